@@ -174,6 +174,23 @@ def cpu_baseline(weights, latent, n_ddim):
   }
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+  """Saves each array as path/<name>.npy in float32.  If together they exceed DUMP_LIMIT_BYTES, each is
+  replaced by the same fixed fraction of its flattened elements, at indices drawn from a seeded generator
+  (sorted; the same for the same shapes in every run)."""
+  os.makedirs(path, exist_ok=True)
+  arrays = {name: np.asarray(a, dtype=np.float32) for name, a in arrays.items()}
+  total = sum(a.nbytes for a in arrays.values())
+  for name, a in arrays.items():
+    if total > DUMP_LIMIT_BYTES:
+      keep = a.size * (DUMP_LIMIT_BYTES - 4096 * len(arrays)) // total
+      a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+    np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument("--gpus", type=int, default=1)
@@ -201,9 +218,14 @@ def main():
                        "multi-rank path of this script runs in seconds; the JSON line says so and is not a benchmark")
   ap.add_argument("--dump-images", default=None,
                   help="rank 0 saves the gathered uint8 images of the last pass to this .npy file")
+  ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                  help="rank 0 writes what the last timed step computed to DIR/<name>.npy (float32): images = the "
+                       "sampler's decoded images, images_uint8 = the gathered uint8 images")
   ap.add_argument("--first-sample-index", type=int, default=None,
                   help="global index of this process's first sample (default: rank * batch-per-gpu)")
   args = ap.parse_args()
+  if args.steps < 1:
+    ap.error("--steps must be at least 1")
   preset = CONFIGS[args.config]
   for k, v in preset.items():
     if getattr(args, k) is None:
@@ -288,6 +310,10 @@ def main():
   torch.cuda.synchronize()
   elapsed = time.perf_counter() - t0
   elapsed = D.max_over_ranks(elapsed, dev)
+  if rank == 0 and args.dump_outputs:
+    # host copies now: the variant pass below reuses the uint8 buffer
+    dump_outputs(args.dump_outputs, {"images": last_f32.float().cpu().numpy(),
+                                     "images_uint8": out.cpu().numpy()})
   ms_unet_step = float(np.mean([a.elapsed_time(b) / n for a, b, n in loop_ms]))
   assert tuple(out.shape) == (world * B, 8 * args.latent, 8 * args.latent, 3) and out.dtype == torch.uint8
   assert bool(torch.isfinite(last_f32.float()).all()), "non-finite images"

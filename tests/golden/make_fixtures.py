@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Generates the committed fixtures in tests/golden/ (run in the build container,
-where /root/reference is mounted; nothing here is needed at test time).
+"""Generates the committed fixtures in tests/golden/ (nothing here is needed at test time):
+
+    python tests/golden/make_fixtures.py <reference tree>     # every fixture
+    python tests/golden/make_fixtures.py --oracle-pins-only    # oracle_pins.json alone
 
   token_ids.json     : `prompt_ids` / `empty_ids` are the ids the reference hard-codes at
                        convert_ckpt_pytorch_to_tf2.py:384-392 (typed in below as data and
@@ -10,9 +12,21 @@ where /root/reference is mounted; nothing here is needed at test time).
   schedule_kats.json : integer DDIM step tables (closed form of model_runners.py:406-409,
                        last N=50 step pinned to 981 by convert_ckpt_pytorch_to_tf2.py:402)
                        and two alphas_cumprod spot values from the oracle.
+  bert_vocab.txt     : the reference's bert_model/vocab.txt (BERT uncased, 30522 tokens),
+                       stored unchanged: the tokenizer tests read it.
+  all_in_one_config.yaml : the reference's YAML, stored unchanged: tests/test_config_cpu.py
+                       binds its sections to this build's constructors.
+  converter_weight_lists.json : what the four list-building functions of
+                       convert_ckpt_pytorch_to_tf2.py:23-338 return, as data: per function the
+                       ordered list of [checkpoint key, layout ops applied to it], recorded by
+                       running them on symbolic tensors (tests/test_converter_pin_cpu.py replays
+                       it against checkpoint.py / weights.py).
 """
+import argparse
+import ast
 import json
 import os
+import shutil
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -68,13 +82,103 @@ def oracle_pins():
   return out
 
 
+class _Sym:
+  """Shape-free stand-in for a checkpoint tensor that records the layout ops applied to it."""
+
+  def __init__(self, key, ops=()):
+    self.key, self.ops = key, tuple(ops)
+
+  @property
+  def T(self):
+    return _Sym(self.key, self.ops + (["T"],))
+
+  def transpose(self, *axes):
+    axes = axes[0] if len(axes) == 1 and isinstance(axes[0], (tuple, list)) else axes
+    return _Sym(self.key, self.ops + (["transpose", [int(a) for a in axes]],))
+
+  def squeeze(self):
+    return _Sym(self.key, self.ops + (["squeeze"],))
+
+  def reshape(self, *shape):
+    shape = shape[0] if len(shape) == 1 and isinstance(shape[0], (tuple, list)) else shape
+    return _Sym(self.key, self.ops + (["reshape", [int(d) for d in shape]],))
+
+
+# What the four list-building functions are made of (checked before anything of them executes): plain
+# data flow -- loops, subscripts, list.append, the four layout transforms -- and nothing that could
+# reach outside: no imports, no attribute other than the transforms, no call other than range / str /
+# the functions' own nested helpers, no decorators, no default arguments, no dunder names.
+_NODES = {"Add", "Assign", "Attribute", "BinOp", "Call", "Compare", "Constant", "Continue", "Dict", "Eq", "Expr",
+          "For", "FormattedValue", "FunctionDef", "If", "In", "JoinedStr", "List", "Load", "Mult", "Name", "Return",
+          "Store", "Subscript", "Tuple", "USub", "UnaryOp", "arg", "arguments", "Sub", "NotEq", "NotIn", "Lt", "Gt",
+          "LtE", "GtE", "And", "Or", "BoolOp", "Not", "Slice", "AugAssign", "Pass", "Break"}
+_ATTRS = {"append", "extend", "transpose", "T", "reshape", "squeeze"}
+CONVERTER_FUNCTIONS = ("get_transformer_weights", "get_unet_weights", "get_decoder_weights", "get_encoder_weights")
+
+
+def _vet(fn):
+  local_defs = {n.name for n in ast.walk(fn) if isinstance(n, ast.FunctionDef)}
+  for n in ast.walk(fn):
+    kind = type(n).__name__
+    assert kind in _NODES, f"{fn.name}: unexpected construct {kind} (line {getattr(n, 'lineno', '?')})"
+    if isinstance(n, ast.FunctionDef):
+      assert not n.decorator_list and not n.args.defaults and not n.args.kw_defaults and \
+          n.args.vararg is None and n.args.kwarg is None, f"{fn.name}: decorators / defaults in {n.name}"
+    if isinstance(n, ast.Attribute):
+      assert n.attr in _ATTRS, f"{fn.name}: attribute .{n.attr}"
+    if isinstance(n, ast.Name):
+      assert not n.id.startswith("__"), f"{fn.name}: name {n.id}"
+    if isinstance(n, ast.Call) and isinstance(n.func, ast.Name):
+      assert n.func.id in {"range", "str"} | local_defs, f"{fn.name}: call to {n.func.id}"
+
+
+def converter_weight_lists(ref):
+  """converter_weight_lists.json: the four functions are cut out of the converter with `ast`, vetted,
+  and run on a recording dict of symbolic tensors; every key they read is one they return."""
+  path = os.path.join(ref, "convert_ckpt_pytorch_to_tf2.py")
+  tree = ast.parse(open(path).read())
+  fns = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name in CONVERTER_FUNCTIONS]
+  assert sorted(f.name for f in fns) == sorted(CONVERTER_FUNCTIONS)
+  for f in fns:
+    _vet(f)
+  # only these four (vetted) defs run, and with two builtins: the reference tree is untrusted content
+  ns = {"__builtins__": {"range": range, "str": str}}
+  exec(compile(ast.Module(body=fns, type_ignores=[]), path, "exec"), ns)
+  out = {}
+  for name in CONVERTER_FUNCTIONS:
+    reads = []
+
+    class Rec(dict):
+      def __missing__(self, key):
+        reads.append(key)
+        return _Sym(key)
+
+    got = ns[name](Rec())
+    assert sorted(reads) == sorted(s.key for s in got), name
+    out[name] = [[s.key, [list(o) for o in s.ops]] for s in got]
+  with open(os.path.join(HERE, "converter_weight_lists.json"), "w") as f:      # one weight per line
+    f.write("{\n" + ",\n".join(json.dumps(name) + ": [\n" + ",\n".join(json.dumps(e) for e in out[name]) + "\n]"
+                               for name in CONVERTER_FUNCTIONS) + "\n}\n")
+  return out
+
+
 def main():
-  if "--oracle-pins-only" in sys.argv:
+  ap = argparse.ArgumentParser()
+  ap.add_argument("reference", nargs="?", help="root of the reference tree (bert_model/, the YAML, the converter)")
+  ap.add_argument("--oracle-pins-only", action="store_true")
+  args = ap.parse_args()
+  if args.oracle_pins_only:
     oracle_pins()
     return
+  if not args.reference:
+    ap.error("the reference tree is needed for every fixture but oracle_pins.json")
+  vocab = os.path.join(args.reference, "bert_model", "vocab.txt")
+  shutil.copyfile(vocab, os.path.join(HERE, "bert_vocab.txt"))
+  shutil.copyfile(os.path.join(args.reference, "all_in_one_config.yaml"), os.path.join(HERE, "all_in_one_config.yaml"))
+  converter_weight_lists(args.reference)
   os.environ["HF_HUB_OFFLINE"] = "1"
   from transformers import BertTokenizerFast
-  tok = BertTokenizerFast.from_pretrained("/root/reference/bert_model")
+  tok = BertTokenizerFast.from_pretrained(os.path.dirname(vocab))
   enc = lambda s: tok(s, truncation=True, max_length=77, padding="max_length")["input_ids"]
   assert enc(PROMPT) == PROMPT_IDS and enc("") == EMPTY_IDS
   out = {"prompt": PROMPT, "prompt_ids": PROMPT_IDS, "empty_ids": EMPTY_IDS,

@@ -2,30 +2,28 @@
 (the ordered key lists of convert_ckpt_pytorch_to_tf2.py:23-372 are the one
 thing the reference holds that fixes variable order and layout).
 
-Runs in the build container only (the reference does not travel to the GPU box).  Nothing of
-the converter is stored here: at test time its four pure list-building functions
-(get_transformer_weights / get_unet_weights / get_decoder_weights / get_encoder_weights; they
-touch nothing but `sd[...]` and array methods) are cut out of the file with `ast`, executed
-against a recording dict of SYMBOLIC arrays (shape + the sequence of .T / .transpose / .squeeze /
-.reshape applied), and the recorded (checkpoint key, transform, resulting shape) list is compared,
-IN ORDER, with this build's manifests and name rules:
+Nothing of the converter's code is stored here.  tests/golden/converter_weight_lists.json holds,
+as data, what its four pure list-building functions (get_transformer_weights / get_unet_weights /
+get_decoder_weights / get_encoder_weights) return: per function the ordered list of checkpoint keys
+and the layout ops (.T / .transpose / .squeeze / .reshape) applied to each (tests/golden/make_fixtures.py
+records it by running them on symbolic tensors).  At test time the lists are replayed against a dict of
+SYMBOLIC arrays (shape + the sequence of ops applied), and the recorded (checkpoint key, transform,
+resulting shape) list is compared, IN ORDER, with this build's manifests and name rules:
   (i)   the key set equals the union of checkpoint.py's rule keys (per model);
   (ii)  the order equals the manifest order of weights.py (= Keras variable creation order, which
         is what `set_weights(list)` relies on, convert_...:399,:410,:417-429);
   (iii) each key's transform is the rule's transform (conv OIHW->HWIO, Linear .T, 1x1 conv
         squeeze().T, attention split / merge reshapes) and yields the manifest's shape.
 """
-import ast
+import json
 import os
 
 import numpy as np
-import pytest
 
 from ldm_tf2_amd import checkpoint as C
 from ldm_tf2_amd import weights as W
 
-REF = "/root/reference/convert_ckpt_pytorch_to_tf2.py"
-pytestmark = pytest.mark.skipif(not os.path.isfile(REF), reason="reference tree not present (GPU box)")
+LISTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "converter_weight_lists.json")
 
 
 class Sym:
@@ -100,43 +98,21 @@ def _pt_shape(kind, fn, shape):
 
 
 def _converter_functions():
-  tree = ast.parse(open(REF).read())
-  want = {"get_transformer_weights", "get_unet_weights", "get_decoder_weights", "get_encoder_weights"}
-  fns = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name in want]
-  assert {f.name for f in fns} == want
-  for f in fns:
-    _vet(f)
-  # only these four (vetted) defs run, and with two builtins: the reference tree is untrusted content
-  ns = {"__builtins__": {"range": range, "str": str}}
-  exec(compile(ast.Module(body=fns, type_ignores=[]), REF, "exec"), ns)
-  return ns
+  """name -> a function that, like the converter's, returns its weight list from a state dict `sd`."""
+  lists = json.load(open(LISTS))
 
+  def replay(entries):
+    def fn(sd):
+      out = []
+      for key, ops in entries:
+        t = sd[key]
+        for op in ops:
+          t = t.T if op[0] == "T" else getattr(t, op[0])(*op[1:])
+        out.append(t)
+      return out
+    return fn
 
-# What the four list-building functions are made of (checked before anything of them executes): plain
-# data flow -- loops, subscripts, list.append, the four layout transforms -- and nothing that could
-# reach outside: no imports, no attribute other than the transforms, no call other than range / str /
-# the functions' own nested helpers, no decorators, no default arguments, no dunder names.
-_NODES = {"Add", "Assign", "Attribute", "BinOp", "Call", "Compare", "Constant", "Continue", "Dict", "Eq", "Expr",
-          "For", "FormattedValue", "FunctionDef", "If", "In", "JoinedStr", "List", "Load", "Mult", "Name", "Return",
-          "Store", "Subscript", "Tuple", "USub", "UnaryOp", "arg", "arguments", "Sub", "NotEq", "NotIn", "Lt", "Gt",
-          "LtE", "GtE", "And", "Or", "BoolOp", "Not", "Slice", "AugAssign", "Pass", "Break"}
-_ATTRS = {"append", "extend", "transpose", "T", "reshape", "squeeze"}
-
-
-def _vet(fn):
-  local_defs = {n.name for n in ast.walk(fn) if isinstance(n, ast.FunctionDef)}
-  for n in ast.walk(fn):
-    kind = type(n).__name__
-    assert kind in _NODES, f"{fn.name}: unexpected construct {kind} (line {getattr(n, 'lineno', '?')})"
-    if isinstance(n, ast.FunctionDef):
-      assert not n.decorator_list and not n.args.defaults and not n.args.kw_defaults and \
-          n.args.vararg is None and n.args.kwarg is None, f"{fn.name}: decorators / defaults in {n.name}"
-    if isinstance(n, ast.Attribute):
-      assert n.attr in _ATTRS, f"{fn.name}: attribute .{n.attr}"
-    if isinstance(n, ast.Name):
-      assert not n.id.startswith("__"), f"{fn.name}: name {n.id}"
-    if isinstance(n, ast.Call) and isinstance(n.func, ast.Name):
-      assert n.func.id in {"range", "str"} | local_defs, f"{fn.name}: call to {n.func.id}"
+  return {name: replay(entries) for name, entries in lists.items()}
 
 
 def _recorded(fn, rules, manifest):

@@ -14,7 +14,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-REF_VOCAB = "/root/reference/bert_model"
+REF_VOCAB = os.path.join(GOLD, "bert_vocab.txt")      # the reference's bert_model/vocab.txt, unchanged
 
 
 # ---- C ABI --------------------------------------------------------------------------
@@ -118,7 +118,6 @@ def test_token_id_fixture_shape():
   assert g["empty_ids"][:3] == [101, 102, 0]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_VOCAB), reason="reference vocab.txt not present on this box")
 def test_tokenizer_against_reference_pins():
   """convert_ckpt_pytorch_to_tf2.py:384-392 hard-codes these ids."""
   from ldm_tf2_amd.tokenizer import BertWordPieceTokenizer, get_token_ids
