@@ -360,6 +360,40 @@ int ldm_cfg_ddim_update(const float* eps_all, const float* xt, const float* nois
                         int dec_index, float guidance_scale, int clip_denoised, int B,
                         int64_t n_per_sample, void* stream);
 
+/*
+ * ldm_cfg_ddim_update + masked inpainting (img2img; CompVis DDIMSampler's mask / x0 convention, 1 = keep).
+ * Same arguments and arithmetic as ldm_cfg_ddim_update; then, with idx = *index read like it and idx >= 1,
+ * the output is blended for the NEXT step (DDIM index j = idx - 1) before it is written to xt_out and to both
+ * halves of x_unet_out:
+ *   o <- m * (q_coef[j][0] * z0 + q_coef[j][1] * Q[j]) + (1 - m) * o
+ * i.e. m * q_sample(z0, steps[j], Q[j]) + (1 - m) * o (model_runners.py:580-600, LatentDiffusionModelTrainer.
+ * q_sample).  At idx = 0 nothing is blended (that output is decoded as it is) and no table is read at -1.
+ * z0 [B][n]; mask [B][n / channels] float32, broadcast over the channels; Q row j at q_noise + j * q_index_stride;
+ * q_coef = device table [N_steps][2] of float32 (sqrt_ac, sqrt_1m_ac) at steps[j] (the `_extract` cast-then-
+ * gather, :41-44).  One launch, like the unmasked entry: the blend adds no launch to a step.
+ */
+int ldm_cfg_ddim_update_masked(const float* eps_all, const float* xt, const float* noise,
+                               int64_t noise_index_stride, float* xt_out, float* pred_x0_out,
+                               void* x_unet_out, int x_dtype, const float* coef, int32_t* index,
+                               int dec_index, float guidance_scale, int clip_denoised, int B,
+                               int64_t n_per_sample, const float* z0, const float* mask,
+                               const float* q_noise, int64_t q_index_stride, const float* q_coef,
+                               int channels, void* stream);
+
+/*
+ * Forward diffusion (model_runners.py:580-600, LatentDiffusionModelTrainer.q_sample):
+ *   xt[b] = sqrt_ac[t[b]] * x0[b] + sqrt_1m_ac[t[b]] * noise[b], float32.
+ * x0 / noise / xt_out [B][n]; t int32 [B] on the device (DDPM timesteps, clamped to [0, num_steps)); the two
+ * tables [num_steps] are the float32 casts of sqrt(abar) and sqrt(1 - abar) (:389-390, `_extract` casts then
+ * gathers).  noise is read at noise + (*index) * noise_index_stride when `index` is non-NULL (a [N][B][n] table
+ * indexed by a device-resident DDIM index), else at noise.  x_unet_out (optional, dtype x_dtype) receives
+ * concat([xt, xt]), the U-Net input of an img2img loop's first step.
+ */
+int ldm_q_sample(const float* x0, const float* noise, int64_t noise_index_stride, const int32_t* index,
+                 const int32_t* t, const float* sqrt_alphas_cumprod, const float* sqrt_one_minus_alphas_cumprod,
+                 int num_steps, float* xt_out, void* x_unet_out, int x_dtype, int B, int64_t n_per_sample,
+                 void* stream);
+
 /* decode_first_stage prologue (model_runners.py:426 + autoencoder.py:362,434):
  * out = Dense_{C->C}(latents / scale_factor), C <= 8; float32 in, out_dtype out. */
 int ldm_post_quant(const float* latents, float scale_factor, const float* kernel_io,

@@ -246,8 +246,45 @@ __global__ __launch_bounds__(256) void gemv_kernel(const float* __restrict__ x, 
   }
 }
 
-// ---- CFG + DDIM update --------------------------------------------------------------
+// ---- forward diffusion q(x_t | x_0) -------------------------------------------------
+// model_runners.py:580-600: xt = _extract(sqrt_ac, t) * x0 + _extract(sqrt_1m_ac, t) * eps, the coefficients
+// float32 (cast, then gathered).  One inline body serves ldm_q_sample and the blend of the masked DDIM update, so
+// a kept latent cell is bit for bit the q_sample of its init latent.
+__device__ __forceinline__ float q_sample_f(float sa, float sb, float x0, float eps) { return sa * x0 + sb * eps; }
+
 template <typename TX>
+__global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__ x0, const float* __restrict__ noise,
+                                                       int64_t noise_stride, const int32_t* index,
+                                                       const int32_t* __restrict__ t,
+                                                       const float* __restrict__ sqrt_ac,
+                                                       const float* __restrict__ sqrt_1m_ac, int num_steps,
+                                                       float* __restrict__ xt_out, TX* __restrict__ x_unet, int B,
+                                                       int64_t n) {
+  if (index) noise += (int64_t)(*index) * noise_stride;
+  const int64_t total = (int64_t)B * n;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    int ti = t[i / n];
+    ti = ti < 0 ? 0 : (ti >= num_steps ? num_steps - 1 : ti);      // (a stray t reads a valid row)
+    const float o = q_sample_f(sqrt_ac[ti], sqrt_1m_ac[ti], x0[i], noise[i]);
+    xt_out[i] = o;
+    if (x_unet) { stf<TX>(x_unet + i, o); stf<TX>(x_unet + total + i, o); }
+  }
+}
+
+// ---- CFG + DDIM update (+ inpainting blend) -----------------------------------------------
+// Blend = false is ldm_cfg_ddim_update.  Blend = true (ldm_cfg_ddim_update_masked) pins the kept cells to the
+// init latent before the NEXT step (index idx - 1) reads them: o <- m * q_sample(z0, steps[idx-1], Q[idx-1])
+// + (1 - m) * o, skipped at idx = 0 (its output goes to the decoder as it is).
+struct BlendArgs {
+  const float* z0;        // [B][n]
+  const float* mask;      // [B][n / channels]
+  const float* q_noise;   // Q table, row j at q_noise + j * q_stride
+  int64_t q_stride;
+  const float* q_coef;    // [N_steps][2]: (sqrt_ac, sqrt_1m_ac) at steps[j], float32
+  int channels;
+};
+
+template <typename TX, bool Blend>
 __global__ __launch_bounds__(256) void cfg_ddim_kernel(const float* __restrict__ eps_all,
                                                        const float* __restrict__ xt,
                                                        const float* __restrict__ noise,
@@ -256,13 +293,24 @@ __global__ __launch_bounds__(256) void cfg_ddim_kernel(const float* __restrict__
                                                        float* __restrict__ pred_x0_out,
                                                        TX* __restrict__ x_unet, const float* coef,
                                                        int32_t* index, int dec_index, float gs,
-                                                       int clip, int B, int64_t n) {
+                                                       int clip, int B, int64_t n, BlendArgs bl) {
   const int idx = *index;
   if (noise) noise += (int64_t)idx * noise_stride;
   const float c1 = coef[idx * 4 + 0], c2 = coef[idx * 4 + 1];
   const float a_prev = coef[idx * 4 + 2], sigma = coef[idx * 4 + 3];
   const float sa = sqrtf(a_prev);
   const float sb = sqrtf(1.0f - a_prev - sigma * sigma);
+  bool blend = false;
+  float qa = 0.f, qb = 0.f;
+  const float* qn = nullptr;
+  if constexpr (Blend) {
+    blend = idx >= 1;                                // never reads a table at -1
+    if (blend) {
+      qa = bl.q_coef[(idx - 1) * 2 + 0];
+      qb = bl.q_coef[(idx - 1) * 2 + 1];
+      qn = bl.q_noise + (int64_t)(idx - 1) * bl.q_stride;
+    }
+  }
   const int64_t total = (int64_t)B * n;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const float eu = eps_all[i], ec = eps_all[total + i];
@@ -271,7 +319,14 @@ __global__ __launch_bounds__(256) void cfg_ddim_kernel(const float* __restrict__
     float x0 = c1 * x - c2 * eps;
     if (clip) x0 = fminf(fmaxf(x0, -1.f), 1.f);
     const float mean = sa * x0 + sb * eps;
-    const float o = mean + (noise ? noise[i] : 0.f) * sigma;
+    float o = mean + (noise ? noise[i] : 0.f) * sigma;
+    if constexpr (Blend) {
+      if (blend) {
+        const float m = bl.mask[i / bl.channels];    // i = (b * n + pixel * channels + c) -> b * (n / channels) + pixel
+        const float q = q_sample_f(qa, qb, bl.z0[i], qn[i]);
+        o = m * q + (1.f - m) * o;
+      }
+    }
     xt_out[i] = o;
     if (pred_x0_out) pred_x0_out[i] = x0;
     if (x_unet) { stf<TX>(x_unet + i, o); stf<TX>(x_unet + total + i, o); }
@@ -541,6 +596,30 @@ extern "C" int ldm_gemv(const float* x, int64_t ldx, const void* wt, const float
   return ldm_launch_status("ldm_gemv");
 }
 
+template <bool Blend>
+static int cfg_ddim_launch(const char* what, const float* eps_all, const float* xt, const float* noise,
+                           int64_t noise_index_stride, float* xt_out, float* pred_x0_out, void* x_unet_out,
+                           int x_dtype, const float* coef, int32_t* index, int dec_index, float guidance_scale,
+                           int clip_denoised, int B, int64_t n_per_sample, const BlendArgs& bl, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  dim3 g(grid_for((int64_t)B * n_per_sample, 256, 1024));
+  if (x_dtype == LDM_BF16)
+    hipLaunchKernelGGL((cfg_ddim_kernel<bf16_t, Blend>), g, dim3(256), 0, s, eps_all, xt, noise, noise_index_stride,
+                       xt_out, pred_x0_out, (bf16_t*)x_unet_out, coef, index, dec_index, guidance_scale,
+                       clip_denoised, B, n_per_sample, bl);
+  else
+    hipLaunchKernelGGL((cfg_ddim_kernel<float, Blend>), g, dim3(256), 0, s, eps_all, xt, noise, noise_index_stride,
+                       xt_out, pred_x0_out, (float*)x_unet_out, coef, index, dec_index, guidance_scale,
+                       clip_denoised, B, n_per_sample, bl);
+  int st = ldm_launch_status(what);
+  if (st != LDM_OK) return st;
+  if (dec_index) {
+    hipLaunchKernelGGL(dec_index_kernel, dim3(1), dim3(1), 0, s, index);
+    st = ldm_launch_status(what);
+  }
+  return st;
+}
+
 extern "C" int ldm_cfg_ddim_update(const float* eps_all, const float* xt, const float* noise,
                                    int64_t noise_index_stride, float* xt_out, float* pred_x0_out,
                                    void* x_unet_out, int x_dtype, const float* coef,
@@ -548,23 +627,49 @@ extern "C" int ldm_cfg_ddim_update(const float* eps_all, const float* xt, const 
                                    int clip_denoised, int B, int64_t n_per_sample, void* stream) {
   LDM_CHECK_ARG(eps_all && xt && xt_out && coef && index, "ldm_cfg_ddim_update: null pointer");
   LDM_CHECK_ARG(DT_OK(x_dtype) && B > 0 && n_per_sample > 0, "ldm_cfg_ddim_update: bad args");
+  return cfg_ddim_launch<false>("ldm_cfg_ddim_update", eps_all, xt, noise, noise_index_stride, xt_out, pred_x0_out,
+                                x_unet_out, x_dtype, coef, index, dec_index, guidance_scale, clip_denoised, B,
+                                n_per_sample, BlendArgs{}, stream);
+}
+
+extern "C" int ldm_cfg_ddim_update_masked(const float* eps_all, const float* xt, const float* noise,
+                                          int64_t noise_index_stride, float* xt_out, float* pred_x0_out,
+                                          void* x_unet_out, int x_dtype, const float* coef, int32_t* index,
+                                          int dec_index, float guidance_scale, int clip_denoised, int B,
+                                          int64_t n_per_sample, const float* z0, const float* mask,
+                                          const float* q_noise, int64_t q_index_stride, const float* q_coef,
+                                          int channels, void* stream) {
+  LDM_CHECK_ARG(eps_all && xt && xt_out && coef && index && z0 && mask && q_noise && q_coef,
+                "ldm_cfg_ddim_update_masked: null pointer");
+  LDM_CHECK_ARG(DT_OK(x_dtype) && B > 0 && n_per_sample > 0 && channels > 0 && n_per_sample % channels == 0 &&
+                    q_index_stride >= 0,
+                "ldm_cfg_ddim_update_masked: bad args (n_per_sample=%lld, channels=%d)", (long long)n_per_sample,
+                channels);
+  const BlendArgs bl{z0, mask, q_noise, q_index_stride, q_coef, channels};
+  return cfg_ddim_launch<true>("ldm_cfg_ddim_update_masked", eps_all, xt, noise, noise_index_stride, xt_out,
+                               pred_x0_out, x_unet_out, x_dtype, coef, index, dec_index, guidance_scale,
+                               clip_denoised, B, n_per_sample, bl, stream);
+}
+
+extern "C" int ldm_q_sample(const float* x0, const float* noise, int64_t noise_index_stride, const int32_t* index,
+                            const int32_t* t, const float* sqrt_alphas_cumprod,
+                            const float* sqrt_one_minus_alphas_cumprod, int num_steps, float* xt_out,
+                            void* x_unet_out, int x_dtype, int B, int64_t n_per_sample, void* stream) {
+  LDM_CHECK_ARG(x0 && noise && t && sqrt_alphas_cumprod && sqrt_one_minus_alphas_cumprod && xt_out,
+                "ldm_q_sample: null pointer");
+  LDM_CHECK_ARG(DT_OK(x_dtype) && B > 0 && n_per_sample > 0 && num_steps > 0 && noise_index_stride >= 0,
+                "ldm_q_sample: bad args");
   hipStream_t s = (hipStream_t)stream;
   dim3 g(grid_for((int64_t)B * n_per_sample, 256, 1024));
   if (x_dtype == LDM_BF16)
-    hipLaunchKernelGGL(cfg_ddim_kernel<bf16_t>, g, dim3(256), 0, s, eps_all, xt, noise, noise_index_stride, xt_out, pred_x0_out,
-                       (bf16_t*)x_unet_out, coef, index, dec_index, guidance_scale, clip_denoised, B,
-                       n_per_sample);
+    hipLaunchKernelGGL(q_sample_kernel<bf16_t>, g, dim3(256), 0, s, x0, noise, noise_index_stride, index, t,
+                       sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, num_steps, xt_out, (bf16_t*)x_unet_out,
+                       B, n_per_sample);
   else
-    hipLaunchKernelGGL(cfg_ddim_kernel<float>, g, dim3(256), 0, s, eps_all, xt, noise, noise_index_stride, xt_out, pred_x0_out,
-                       (float*)x_unet_out, coef, index, dec_index, guidance_scale, clip_denoised, B,
-                       n_per_sample);
-  int st = ldm_launch_status("ldm_cfg_ddim_update");
-  if (st != LDM_OK) return st;
-  if (dec_index) {
-    hipLaunchKernelGGL(dec_index_kernel, dim3(1), dim3(1), 0, s, index);
-    st = ldm_launch_status("ldm_cfg_ddim_update(dec)");
-  }
-  return st;
+    hipLaunchKernelGGL(q_sample_kernel<float>, g, dim3(256), 0, s, x0, noise, noise_index_stride, index, t,
+                       sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, num_steps, xt_out, (float*)x_unet_out,
+                       B, n_per_sample);
+  return ldm_launch_status("ldm_q_sample");
 }
 
 extern "C" int ldm_select_row(const float* table, int64_t ld, int rows, int cols, int32_t* index, int pre_decrement,

@@ -13,6 +13,11 @@ inside the loop.  One DDIM step = one U-Net forward on [xt; xt] + one fused
 CFG/DDIM-update kernel that reads its coefficients from a device table at a
 device-resident index and decrements it, so a step has no host-side scalars and
 the whole step can be captured once in a HIP graph and replayed N times.
+
+img2img / inpainting run the same step from an intermediate DDIM
+index: the start latent is the forward diffusion (q_sample, the reference trainer's
+:580-600) of the encoded init image, and a mask pins kept latent cells to it inside the
+step's one update launch.
 """
 from __future__ import annotations
 
@@ -39,15 +44,47 @@ def _extract(data, t):
   return np.asarray(data).astype(np.float32)[np.asarray(t)].reshape(-1, 1, 1, 1)
 
 
-def normal_latents(seed, first_index, count, shape_hwc):
+def normal_latents(seed, first_index, count, shape_hwc, stream=None):
   """x_T ~ N(0,1): sample i of a run is drawn from its own generator keyed by
   (seed, global sample index), so a sample's trajectory does not depend on how
-  samples are spread over GPUs."""
+  samples are spread over GPUs.  `stream` (an int) keys a third entropy word: the
+  img2img draws (ENCODE_STREAM, Q_STREAM + i) never share a generator with the x_T
+  stream (seed) or the eta-noise streams (seed + 1 + i), which have two words."""
   out = np.empty((count,) + tuple(shape_hwc), dtype=np.float32)
   for i in range(count):
-    g = np.random.default_rng([int(seed), int(first_index) + i])
+    key = [int(seed), int(first_index) + i] + ([] if stream is None else [int(stream)])
+    g = np.random.default_rng(key)
     out[i] = g.standard_normal(shape_hwc, dtype=np.float32)
   return out
+
+
+ENCODE_STREAM = 1 << 30          # posterior noise E of get_latents
+Q_STREAM = (1 << 30) + 1         # + i: forward-diffusion noise Q[i] of DDIM index i
+
+
+def img2img_start(strength, num_ddim_steps):
+  """k = int(strength * N) (CompVis's t_enc): the loop runs DDIM indices k-1 .. 0."""
+  strength = float(strength)
+  if not 0. < strength <= 1.:
+    raise ValueError(f"strength must be in (0, 1], got {strength}")
+  k = int(strength * num_ddim_steps)
+  if k < 1:
+    raise ValueError(f"strength {strength} runs int({strength} * {num_ddim_steps}) = 0 DDIM steps")
+  return k
+
+
+def latent_mask(pixel_mask, f):
+  """Pixel mask [B,H,W] (or [H,W]; nonzero = keep) -> float32 [B,H/f,W/f] by a min-pool over
+  each f x f cell: a latent cell is kept only if all its pixels are, so every pixel marked for
+  regeneration is regenerated."""
+  m = np.asarray(pixel_mask.cpu() if isinstance(pixel_mask, torch.Tensor) else pixel_mask)
+  if m.ndim == 2:
+    m = m[None]
+  if m.ndim != 3 or m.shape[1] % f or m.shape[2] % f:
+    raise ValueError(f"pixel mask of shape {m.shape} is not [B,H,W] with H, W multiples of {f}")
+  B, H, W = m.shape
+  keep = (m != 0).reshape(B, H // f, f, W // f, f).all(axis=(2, 4))
+  return keep.astype(np.float32)
 
 
 class LatentDiffusionModel(object):
@@ -91,9 +128,13 @@ class LatentDiffusionModel(object):
     # :420-423
     self._ddim_sqrt_recip_alphas_cumprod = self._sqrt_recip_alphas_cumprod[self._ddim_steps]
     self._ddim_sqrt_recipm1_alphas_cumprod = self._sqrt_recipm1_alphas_cumprod[self._ddim_steps]
+    # :389-390 (LatentDiffusionModelTrainer.q_sample's tables)
+    self._sqrt_alphas_cumprod = np.sqrt(self._alphas_cumprod)
+    self._sqrt_one_minus_alphas_cumprod = np.sqrt(1. - self._alphas_cumprod)
 
     self.device = getattr(unet, "device", torch.device("cuda:0"))
     self._tables = None
+    self._q_tables = None
 
   def _device_tables(self):
     """Device copies of the schedule, made on first use: per DDIM index the row
@@ -106,6 +147,50 @@ class LatentDiffusionModel(object):
                       torch.from_numpy(self._ddim_steps.copy()).to(self.device),
                       torch.zeros(1, dtype=torch.int32, device=self.device))
     return self._tables
+
+  def _device_q_tables(self):
+    """Device copies of the forward-diffusion tables after the float32 cast of `_extract`: sqrt(abar) and
+    sqrt(1 - abar) [num_steps], and per DDIM index the pair gathered at its step [N,2]."""
+    if self._q_tables is None:
+      sa = self._sqrt_alphas_cumprod.astype(np.float32)
+      sb = self._sqrt_one_minus_alphas_cumprod.astype(np.float32)
+      per_index = np.stack([sa[self._ddim_steps], sb[self._ddim_steps]], axis=1)
+      self._q_tables = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(self.device) for a in (sa, sb, per_index))
+    return self._q_tables
+
+  def q_sample(self, x0, t, eps):
+    """model_runners.py:580-600 (LatentDiffusionModelTrainer.q_sample): _extract(sqrt_ac, t) * x0 +
+    _extract(sqrt_1m_ac, t) * eps.  x0, eps [B,h,w,c]; t int [B] DDPM timesteps.  float32, on the device."""
+    x0 = torch.as_tensor(x0, dtype=torch.float32).to(self.device).contiguous()
+    eps = torch.as_tensor(eps, dtype=torch.float32).to(self.device).contiguous()
+    t = torch.as_tensor(np.asarray(t) if not isinstance(t, torch.Tensor) else t).to(self.device, torch.int32)
+    t = t.reshape(-1).contiguous()
+    if tuple(eps.shape) != tuple(x0.shape) or t.numel() != x0.shape[0]:
+      raise ValueError(f"q_sample: x0 {tuple(x0.shape)}, eps {tuple(eps.shape)}, t {tuple(t.shape)}")
+    sa, sb, _ = self._device_q_tables()
+    return ops.q_sample(x0, eps, t, sa, sb, torch.empty_like(x0))
+
+  def get_latents(self, inputs, noise=None, seed=0, first_sample_index=0):
+    """model_runners.py:602-625: images [B,H,W,3] in [-1, 1] -> scale_factor * latents.  KL: a posterior
+    sample (`noise` [B,h,w,c], else drawn from `seed`'s ENCODE_STREAM per global sample index, where the
+    reference draws an unseeded tf.random.normal); VQ: encode(only_encode=True)."""
+    if isinstance(self._autoencoder, AutoencoderKL):
+      posterior = self._autoencoder.encode(inputs)
+      moments = posterior._moments
+      B, h, w, c2 = moments.shape
+      if noise is None:
+        noise = normal_latents(seed, first_sample_index, B, (h, w, c2 // 2), stream=ENCODE_STREAM)
+      noise = torch.as_tensor(np.asarray(noise) if not isinstance(noise, torch.Tensor) else noise,
+                              dtype=torch.float32).to(self.device).contiguous()
+      if tuple(noise.shape) != (B, h, w, c2 // 2):
+        raise ValueError(f"encode noise {tuple(noise.shape)} != latents {(B, h, w, c2 // 2)}")
+      out = torch.empty(B, h, w, c2 // 2, dtype=torch.float32, device=moments.device)
+      # (mean + std * noise) * scale_factor: the sample, then the float32 scale (:624)
+      return ops.gaussian_sample(moments, out, noise=noise, out_scale=np.float32(self._scale_factor))
+    elif isinstance(self._autoencoder, AutoencoderVQ):
+      latents = self._autoencoder.encode(inputs, only_encode=True)
+      return latents * np.float32(self._scale_factor)
+    raise NotImplementedError("Invalid autoencoder")
 
   @property
   def _coef_dev(self):
@@ -173,28 +258,40 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       self._state_key = key
       self._graph = None
 
-  def _noise_table(self, noises, shape):
-    """Per-step noise in a buffer the sampler owns (one per shape): a captured graph reads it
-    at a fixed address, whatever tensor the caller passed."""
-    src = torch.as_tensor(np.asarray(noises) if not isinstance(noises, torch.Tensor) else noises,
-                          dtype=torch.float32)
-    assert tuple(src.shape) == tuple(shape), (tuple(src.shape), tuple(shape))
-    buf = getattr(self, "_noise_buf", None)
+  def _owned(self, name, src, shape, dtype=torch.float32):
+    """`src` copied into a buffer the sampler owns (one per name and shape): a captured graph reads it at a
+    fixed address, whatever tensor the caller passed.  A new buffer drops the captured graph."""
+    src = torch.as_tensor(np.asarray(src) if not isinstance(src, torch.Tensor) else src, dtype=dtype)
+    if tuple(src.shape) != tuple(shape):
+      raise ValueError(f"{name}: shape {tuple(src.shape)}, expected {tuple(shape)}")
+    buf = getattr(self, name, None)
     if buf is None or tuple(buf.shape) != tuple(shape):
-      buf = torch.empty(shape, dtype=torch.float32, device=self.device)
-      self._noise_buf = buf
+      buf = torch.empty(shape, dtype=dtype, device=self.device)
+      setattr(self, name, buf)
       self._graph = None
     buf.copy_(src)
     return buf
 
-  def _step(self, guidance_scale, clip_denoised, noise_table, dec_index, pred_x0_out=None):
-    """unet([xt; xt], t=steps[index]) -> CFG -> DDIM update, all on device."""
+  def _noise_table(self, noises, shape):
+    """Per-step noise in a buffer the sampler owns (one per shape)."""
+    return self._owned("_noise_buf", noises, shape)
+
+  def _step(self, guidance_scale, clip_denoised, noise_table, dec_index, pred_x0_out=None, masked=False):
+    """unet([xt; xt], t=steps[index]) -> CFG -> DDIM update, all on device.  `masked`: the update also pins the
+    kept cells for the next step (img2img inpainting: _z0_buf, _mask_buf, _q_buf; still one launch)."""
     # (paired_rows: x2 = [xt; xt], one timestep -- rows r and r + B differ only in their context, :449-452)
     # The loop counter moves at the START of a step (`dec_index`: the U-Net's first launch pre-decrements it and
     # selects the step's row of the temb table), so a loop starts from index = N and ends at 0.
     self._unet.forward(self._x2, steps=self._steps_dev, index=self._index_dev, out=self._eps, paired_rows=True,
                        **self._temb_kwargs(dec_index))
     stride = 0 if noise_table is None else noise_table[0].numel()
+    if masked:
+      ops.cfg_ddim_update_masked(self._eps, self._xt, self._xt, self._coef_dev, self._index_dev, guidance_scale,
+                                 self._z0_buf, self._mask_buf, self._q_buf, self._device_q_tables()[2],
+                                 noise=noise_table, x_unet_out=self._x2, dec_index=dec_index and not self._pre_dec,
+                                 clip_denoised=clip_denoised, noise_index_stride=stride,
+                                 q_index_stride=self._q_buf[0].numel(), pred_x0_out=pred_x0_out)
+      return
     ops.cfg_ddim_update(self._eps, self._xt, self._xt, self._coef_dev, self._index_dev,
                         guidance_scale, noise=noise_table, x_unet_out=self._x2,
                         dec_index=dec_index and not self._pre_dec, clip_denoised=clip_denoised,
@@ -235,6 +332,54 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     self._unet.set_context(cond)
     self._ctx_shape = tuple(cond.shape)
 
+  def _eta_noise_table(self, noises, seed, first_sample_index, B, h, w, c):
+    """[N,B,h,w,c] per-step noise (read only when eta > 0): `noises`, else per DDIM index i the stream seed + 1 + i."""
+    if self._eta == 0.:
+      return None
+    n = len(self._ddim_steps)
+    if noises is None:
+      noises = np.stack([normal_latents(seed + 1 + i, first_sample_index, B, (h, w, c)) for i in range(n)])
+    return self._noise_table(noises, (n, B, h, w, c))
+
+  def _sample_loop(self, num_steps, reset, step, gkey, record):
+    """Run `num_steps` DDIM steps from the state `reset()` sets (latents, U-Net input and the device counter at
+    _loop_start_index(num_steps)); `step(dec_index)` enqueues one step.  With graphs (and no `record`) one step
+    is captured once per `gkey` -- after a warm-up step on a side stream has allocated every scratch buffer --
+    and replayed num_steps times; the counter lives on the device, so the graph serves any start index."""
+    reset()
+    use_graph = self._use_graph and record is None
+    t0 = torch.cuda.Event(enable_timing=True)
+    t1 = torch.cuda.Event(enable_timing=True)
+    if use_graph:
+      if self._graph is None or self._graph_key != gkey:
+        self._index_dev.fill_(num_steps - 1)         # (the warm-up step does not move the counter)
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+          step(False)
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        reset()
+        g = torch.cuda.CUDAGraph()
+        # thread-local capture mode: in a multi-GPU job the RCCL watchdog thread polls events
+        # while this thread captures; only this thread's calls belong to the capture
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+          step(True)
+        self._graph, self._graph_key = g, gkey
+        reset()
+      t0.record()
+      for _ in range(num_steps):                                          # :484-502
+        self._graph.replay()
+      t1.record()
+    else:
+      t0.record()
+      for _ in range(num_steps):
+        step(True)
+        if record is not None:
+          record.append(self._xt.clone())
+      t1.record()
+    self._loop_events = (t0, t1, num_steps)
+
   def ddim_p_sample_loop(self, cond_model_inputs, shape, guidance_scale=5., x_T=None,
                          noises=None, seed=0, first_sample_index=0, record=None):
     """model_runners.py:474-509.  Extra inputs the reference lacks: `x_T` [B,h,w,4]
@@ -253,65 +398,83 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     cond_combined = context
     self._alloc_state(B, h, w, c)
     self._set_context(cond_combined)
-    noise_table = None
-    if self._eta != 0.:
-      if noises is None:
-        noises = np.stack([normal_latents(seed + 1 + i, first_sample_index, B, (h, w, c))
-                           for i in range(n)])
-      noise_table = self._noise_table(noises, (n, B, h, w, c))
-    self._xt.copy_(xt)
-    self._x2[:B].copy_(xt)
-    self._x2[B:].copy_(xt)
-    self._index_dev.fill_(self._loop_start_index(n))                      # :476 (index = N - 1 in the first step)
+    noise_table = self._eta_noise_table(noises, seed, first_sample_index, B, h, w, c)
 
-    gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape)
-    use_graph = self._use_graph and record is None
-    t0 = torch.cuda.Event(enable_timing=True)
-    t1 = torch.cuda.Event(enable_timing=True)
-    if use_graph:
-      if self._graph is None or self._graph_key != gkey:
-        # warm-up run on a side stream allocates every scratch buffer, then capture
-        self._index_dev.fill_(n - 1)                 # (the warm-up step does not move the counter)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-          self._step(guidance_scale, False, noise_table, dec_index=False)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        self._xt.copy_(xt)
-        self._x2[:B].copy_(xt)
-        self._x2[B:].copy_(xt)
-        g = torch.cuda.CUDAGraph()
-        # thread-local capture mode: in a multi-GPU job the RCCL watchdog thread polls events
-        # while this thread captures; only this thread's calls belong to the capture
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-          self._step(guidance_scale, False, noise_table, dec_index=True)
-        self._graph, self._graph_key = g, gkey
-        self._xt.copy_(xt)
-        self._x2[:B].copy_(xt)
-        self._x2[B:].copy_(xt)
-        self._index_dev.fill_(self._loop_start_index(n))
-      t0.record()
-      for _ in range(n):                                                  # :484-502
-        self._graph.replay()
-      t1.record()
-    else:
-      t0.record()
-      for _ in range(n):
-        self._step(guidance_scale, False, noise_table, dec_index=True)
-        if record is not None:
-          record.append(self._xt.clone())
-      t1.record()
-    self._loop_events = (t0, t1, n)
+    def reset():
+      self._xt.copy_(xt)
+      self._x2[:B].copy_(xt)
+      self._x2[B:].copy_(xt)
+      self._index_dev.fill_(self._loop_start_index(n))                    # :476 (index = N - 1 in the first step)
+
+    gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, False)
+    self._sample_loop(n, reset, lambda dec: self._step(guidance_scale, False, noise_table, dec_index=dec),
+                      gkey, record)
+    return self._finish(self._xt)
+
+  def _finish(self, latents):
     if self._verbose:                                                     # :503
       print(f"[INFO] Done running denoising for {self._num_ddim_steps} steps with"
             f" eta {self._eta}")
       sys.stdout.flush()
-    images = self.decode_first_stage(self._xt)                            # :506
+    images = self.decode_first_stage(latents)                             # :506
     if self._verbose:                                                     # :507
       print("[INFO] Done decoding images from the final latent variable.")
       sys.stdout.flush()
     return images
+
+  def ddim_p_sample_loop_img2img(self, cond_model_inputs, init_images, guidance_scale=5., strength=0.75,
+                                 mask=None, encode_noise=None, q_noises=None, noises=None, seed=0,
+                                 first_sample_index=0, record=None):
+    """img2img (SDEdit) and masked inpainting on the DDIM loop.
+    cond_model_inputs: token ids [uncond x B; cond x B].  init_images [B,H,W,3] (or [H,W,3], tiled) float32
+    in [-1, 1].  z0 = get_latents(init_images, encode_noise); k = int(strength * N); the loop starts from
+    x = q_sample(z0, steps[k-1], Q[k-1]) and runs DDIM indices k-1 .. 0.  `mask` [B,h,w] (or [h,w]) at latent
+    resolution, 1 = keep: before the step at every index i < k-1, x <- m q_sample(z0, steps[i], Q[i]) + (1-m) x.
+    `q_noises` [N,B,h,w,c] (Q, indexed by DDIM index; else seed's Q_STREAM + i per global sample index),
+    `noises` as in ddim_p_sample_loop, `record` receives x after each of the k steps (eager, no graph).
+    Returns the decoded images; the final latents stay in self._xt."""
+    n = len(self._ddim_steps)
+    k = img2img_start(strength, n)
+    B = len(cond_model_inputs) // 2
+    imgs = torch.as_tensor(np.asarray(init_images) if not isinstance(init_images, torch.Tensor) else init_images,
+                           dtype=torch.float32)
+    if imgs.dim() == 3:
+      imgs = imgs[None].expand(B, *imgs.shape)
+    if imgs.dim() != 4 or imgs.shape[0] != B or imgs.shape[-1] != 3:
+      raise ValueError(f"init_images must be [B={B},H,W,3] or [H,W,3], got {tuple(imgs.shape)}")
+    if mask is not None:
+      mask = torch.as_tensor(np.asarray(mask) if not isinstance(mask, torch.Tensor) else mask, dtype=torch.float32)
+      if mask.dim() == 2:
+        mask = mask[None].expand(B, *mask.shape)
+    context = self._cond_stage_model(cond_model_inputs)
+    z0 = self.get_latents(imgs.contiguous(), noise=encode_noise, seed=seed, first_sample_index=first_sample_index)
+    _, h, w, c = z0.shape
+    if mask is not None and tuple(mask.shape) != (B, h, w):
+      raise ValueError(f"mask must be [B,h,w] = {(B, h, w)} (or [h,w]) at latent resolution, "
+                       f"got {tuple(mask.shape)}")
+    self._alloc_state(B, h, w, c)
+    self._set_context(context)
+    noise_table = self._eta_noise_table(noises, seed, first_sample_index, B, h, w, c)
+    if q_noises is None:
+      q_noises = np.zeros((n, B, h, w, c), dtype=np.float32)
+      for i in range(k):                       # (rows >= k are never read)
+        q_noises[i] = normal_latents(seed, first_sample_index, B, (h, w, c), stream=Q_STREAM + i)
+    q_buf = self._owned("_q_buf", q_noises, (n, B, h, w, c))
+    z0_buf = self._owned("_z0_buf", z0, (B, h, w, c))
+    if mask is not None:
+      self._owned("_mask_buf", mask, (B, h, w))
+    t_start = self._owned("_t_buf", np.full(B, self._ddim_steps[k - 1]), (B,), dtype=torch.int32)
+    sa, sb, _ = self._device_q_tables()
+    masked = mask is not None
+
+    def reset():
+      ops.q_sample(z0_buf, q_buf[k - 1], t_start, sa, sb, self._xt, x_unet_out=self._x2)
+      self._index_dev.fill_(self._loop_start_index(k))
+
+    gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, masked)
+    self._sample_loop(k, reset, lambda dec: self._step(guidance_scale, False, noise_table, dec_index=dec,
+                                                        masked=masked), gkey, record)
+    return self._finish(self._xt)
 
   def ddim_p_sample_loop_progressive(self, cond_model_inputs, shape, guidance_scale=5.,
                                      record_freq=5, x_T=None, noises=None, seed=0,
@@ -334,12 +497,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
                          dtype=torch.float32).to(self.device).contiguous()
     self._alloc_state(B, h, w, c)
     self._set_context(context)
-    noise_table = None
-    if self._eta != 0.:
-      if noises is None:
-        noises = np.stack([normal_latents(seed + 1 + i, first_sample_index, B, (h, w, c))
-                           for i in range(n)])
-      noise_table = self._noise_table(noises, (n, B, h, w, c))
+    noise_table = self._eta_noise_table(noises, seed, first_sample_index, B, h, w, c)
     self._xt.copy_(xt)
     self._x2[:B].copy_(xt)
     self._x2[B:].copy_(xt)

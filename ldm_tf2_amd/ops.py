@@ -19,7 +19,7 @@ from ._lib import ACT_GEGLU, ACT_GELU, ACT_NONE, ACT_SILU, BF16, F32, GemmParams
 __all__ = [
     "ACT_NONE", "ACT_GELU", "ACT_GEGLU", "ACT_SILU", "F32", "BF16", "code", "linear", "conv3x3",
     "bmm_nt", "conv3x3_small", "groupnorm", "layernorm", "softmax_rows", "attention",
-    "time_embedding", "gemv", "cfg_ddim_update", "post_quant", "vq_nearest", "embedding",
+    "time_embedding", "gemv", "cfg_ddim_update", "cfg_ddim_update_masked", "q_sample", "post_quant", "vq_nearest", "embedding",
     "minmax_u8", "cast",
 ]
 
@@ -800,6 +800,49 @@ def cfg_ddim_update(eps_all, xt, xt_out, coef, index, guidance_scale, noise=None
                                 int(bool(clip_denoised)), B, n, _stream()), "ldm_cfg_ddim_update")
   return xt_out
 
+
+
+def cfg_ddim_update_masked(eps_all, xt, xt_out, coef, index, guidance_scale, z0, mask, q_noise, q_coef,
+                           noise=None, x_unet_out=None, dec_index=False, clip_denoised=False, noise_index_stride=0,
+                           q_index_stride=0, pred_x0_out=None):
+  """cfg_ddim_update, then (at *index = idx >= 1) o <- m * q_sample(z0, steps[idx-1], Q[idx-1]) + (1 - m) * o:
+  z0 [B,h,w,c], mask [B,h,w] (1 = keep the init image), Q row j at q_noise + j * q_index_stride, q_coef [N,2]."""
+  B = xt.shape[0]
+  n = xt.numel() // B
+  c = xt.shape[-1]
+  assert z0.is_contiguous() and z0.numel() == xt.numel()
+  assert mask.is_contiguous() and mask.numel() * c == xt.numel()
+  assert q_noise.is_contiguous() and q_coef.is_contiguous() and q_coef.shape == (coef.shape[0], 2)
+  assert q_noise.numel() >= (q_coef.shape[0] - 1) * q_index_stride + xt.numel()
+  xd = code(x_unet_out.dtype) if x_unet_out is not None else F32
+  check(lib.ldm_cfg_ddim_update_masked(
+      _ptr(_f32(eps_all, "eps_all")), _ptr(_f32(xt, "xt")), _ptr(_f32(noise, "noise")), int(noise_index_stride),
+      _ptr(_f32(xt_out, "xt_out")), _ptr(_f32(pred_x0_out, "pred_x0_out")), _ptr(x_unet_out), xd,
+      _ptr(_f32(coef, "coef")), _ptr(index), int(bool(dec_index)), float(guidance_scale), int(bool(clip_denoised)),
+      B, n, _ptr(_f32(z0, "z0")), _ptr(_f32(mask, "mask")), _ptr(_f32(q_noise, "q_noise")), int(q_index_stride),
+      _ptr(_f32(q_coef, "q_coef")), c, _stream()), "ldm_cfg_ddim_update_masked")
+  return xt_out
+
+
+def q_sample(x0, noise, t, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, xt_out, x_unet_out=None,
+             index=None, noise_index_stride=0):
+  """xt_out[b] = sqrt_ac[t[b]] * x0[b] + sqrt_1m_ac[t[b]] * noise[b] (float32); t int32 [B] on the device;
+  `index`: noise row *index of a table with `noise_index_stride`; x_unet_out: [xt; xt] in its own dtype."""
+  B = x0.shape[0]
+  n = x0.numel() // B
+  assert x0.is_contiguous() and xt_out.is_contiguous() and xt_out.numel() == x0.numel()
+  assert noise.is_contiguous() and (index is not None or noise.numel() == x0.numel())
+  assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == B
+  assert index is None or index.dtype == torch.int32
+  assert sqrt_alphas_cumprod.numel() == sqrt_one_minus_alphas_cumprod.numel()
+  assert x_unet_out is None or (x_unet_out.is_contiguous() and x_unet_out.numel() == 2 * x0.numel())
+  xd = code(x_unet_out.dtype) if x_unet_out is not None else F32
+  check(lib.ldm_q_sample(_ptr(_f32(x0, "x0")), _ptr(_f32(noise, "noise")), int(noise_index_stride), _ptr(index),
+                         _ptr(t), _ptr(_f32(sqrt_alphas_cumprod, "sqrt_alphas_cumprod")),
+                         _ptr(_f32(sqrt_one_minus_alphas_cumprod, "sqrt_one_minus_alphas_cumprod")),
+                         sqrt_alphas_cumprod.numel(), _ptr(_f32(xt_out, "xt_out")), _ptr(x_unet_out), xd, B, n,
+                         _stream()), "ldm_q_sample")
+  return xt_out
 
 def post_quant(latents, scale_factor, kernel_io, bias, out):
   Cc = latents.shape[-1]

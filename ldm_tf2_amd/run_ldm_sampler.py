@@ -16,6 +16,11 @@ TF checkpoints cannot be read here; `pre_ckpt_paths` entries that point at an
 `pre_ckpt_paths.compvis` naming the original PyTorch checkpoint loads all three models
 through checkpoint.py; anything else falls back to seeded random init with a warning --
 the same observable behaviour.
+
+img2img / inpainting: optional `ldm_sampling` keys `init_image` (a .npy of uint8 [H,W,3] or
+[B,H,W,3], read as x/127.5 - 1), `strength` (default 0.75) and `mask` (a .npy [H,W] or
+[B,H,W], nonzero = keep; needs `init_image`).  With `init_image` the autoencoder is built
+or loaded with its encoder.  Without these keys nothing changes.
 """
 from __future__ import annotations
 
@@ -29,7 +34,7 @@ import yaml
 
 from . import ops
 from .autoencoder import AutoencoderKL, AutoencoderVQ
-from .model_runners import LatentDiffusionModelSampler
+from .model_runners import LatentDiffusionModelSampler, latent_mask
 from .tokenizer import get_token_ids
 from .transformer import TransformerModel
 from .unet import UNet
@@ -70,9 +75,46 @@ def compvis_manifest_configs(config):
   return dict(unet_cfg=unet_cfg, transformer_cfg=dict(config["cond_stage_model"]), autoencoder_cfg=ae_cfg)
 
 
+def needs_encoder(config):
+  """img2img (`ldm_sampling.init_image`) encodes its init image: the autoencoder is built with its encoder."""
+  return bool(config["ldm_sampling"].get("init_image"))
+
+
+def downsampling_factor(config):
+  kind = config["ldm_sampling"]["autoencoder_type"]
+  mult = config["autoencoder_kl" if kind == "kl" else "autoencoder_vq"].get(
+      "multipliers", (1, 2, 4, 4) if kind == "kl" else (1, 2, 2, 4))
+  return 2 ** (len(mult) - 1)
+
+
+def sampling_call(config, token_ids, seed):
+  """(sampler method name, positional args, kwargs) of the call main() makes for `config`."""
+  samp = config["ldm_sampling"]
+  base = (token_ids, samp["latent_shape"], samp["guidance_scale"])
+  if samp.get("mask") is not None and not samp.get("init_image"):
+    raise ValueError("ldm_sampling.mask needs ldm_sampling.init_image")
+  if samp.get("init_image"):
+    if samp.get("sample_save_progress"):
+      raise ValueError("sample_save_progress is not supported with init_image")
+    img = np.load(samp["init_image"])
+    if img.dtype != np.uint8 or img.ndim not in (3, 4) or img.shape[-1] != 3:
+      raise ValueError(f"init_image must be uint8 [H,W,3] or [B,H,W,3], got {img.dtype} {img.shape}")
+    images = img.astype(np.float32) / np.float32(127.5) - np.float32(1.0)
+    kwargs = dict(strength=float(samp.get("strength", 0.75)), seed=seed)
+    if samp.get("mask") is not None:
+      pm = np.load(samp["mask"])
+      lm = latent_mask(pm, downsampling_factor(config))
+      kwargs["mask"] = lm[0] if pm.ndim == 2 else lm          # [h,w]: one mask, tiled over the batch
+    return "ddim_p_sample_loop_img2img", (token_ids, images, samp["guidance_scale"]), kwargs
+  if samp.get("sample_save_progress"):
+    return "ddim_p_sample_loop_progressive", base, dict(seed=seed)
+  return "ddim_p_sample_loop", base, dict(seed=seed)
+
+
 def build_from_config(config, dtype=torch.bfloat16, device="cuda:0", seed=2, use_graph=True,
                       verbose=True):
   ck = dict(config.get("pre_ckpt_paths", {}))
+  with_encoder = needs_encoder(config)
   kind = config["ldm_sampling"]["autoencoder_type"]
   if kind not in ("kl", "vq"):
     raise NotImplementedError("invalid autoencoder type.")
@@ -80,14 +122,15 @@ def build_from_config(config, dtype=torch.bfloat16, device="cuda:0", seed=2, use
   hidden = config["cond_stage_model"]["hidden_size"]
   if ck.get("compvis"):
     # one CompVis PyTorch checkpoint for all three models (checkpoint.py; what the
-    # reference reaches through convert_ckpt_pytorch_to_tf2.py + three TF checkpoints).  The
-    # sampling path decodes only: the checkpoint's encoder is not loaded (its layout differs
-    # between KL, double_z, and VQ); the U-Net's context width is the text model's hidden size;
-    # a VQ decoder's attention blocks depend on the latent size it will run at.
+    # reference reaches through convert_ckpt_pytorch_to_tf2.py + three TF checkpoints).  txt2img
+    # decodes only: the checkpoint's encoder is loaded for img2img alone; the U-Net's context width
+    # is the text model's hidden size; a VQ decoder's attention blocks depend on the latent size it
+    # will run at.
     from .checkpoint import from_compvis_state_dict
     sd = torch.load(ck["compvis"], map_location="cpu", weights_only=True)
     sd = {k: v.float().numpy() for k, v in sd.get("state_dict", sd).items() if torch.is_tensor(v)}
-    loaded = from_compvis_state_dict(sd, **compvis_manifest_configs(config), with_encoder=False, kl=(kind == "kl"))
+    loaded = from_compvis_state_dict(sd, **compvis_manifest_configs(config), with_encoder=with_encoder,
+                                     kl=(kind == "kl"))
     _preloaded.update(loaded)
   transformer = TransformerModel(**config["cond_stage_model"], dtype=dtype, device=device, seed=seed,
                                  weights=_load_weights(ck.get("cond_stage_model"), "cond_stage_model"))
@@ -96,11 +139,13 @@ def build_from_config(config, dtype=torch.bfloat16, device="cuda:0", seed=2, use
               weights=_load_weights(ck.get("unet"), "unet"))
   if kind == "kl":
     autoencoder = AutoencoderKL(**config["autoencoder_kl"], dtype=dtype, device=device, seed=seed,
-                                weights=_load_weights(ck.get("autoencoder"), "autoencoder"))
+                                weights=_load_weights(ck.get("autoencoder"), "autoencoder"),
+                                with_encoder=with_encoder or None)
   elif kind == "vq":
     autoencoder = AutoencoderVQ(**config["autoencoder_vq"], dtype=dtype, device=device, seed=seed,
                                 latent_size=latent_size,
-                                weights=_load_weights(ck.get("autoencoder"), "autoencoder"))
+                                weights=_load_weights(ck.get("autoencoder"), "autoencoder"),
+                                with_encoder=with_encoder or None)
   return LatentDiffusionModelSampler(unet=unet, autoencoder=autoencoder, cond_stage_model=transformer,
                                      use_graph=use_graph, verbose=verbose, **config["ldm"])
 
@@ -109,7 +154,8 @@ def main(argv=None):
   ap = argparse.ArgumentParser()
   ap.add_argument("--config_path", required=True)
   ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
-  ap.add_argument("--seed", type=int, default=0, help="seed of x_T (and of the noise when eta > 0)")
+  ap.add_argument("--seed", type=int, default=0,
+                  help="seed of every draw: x_T, the noise when eta > 0, img2img's encode and q_sample noise")
   ap.add_argument("--out", default="images.npy")
   args = ap.parse_args(argv)
   with open(args.config_path) as f:
@@ -119,10 +165,10 @@ def main(argv=None):
   samp = config["ldm_sampling"]
   token_ids = get_token_ids(samp["text_prompt"], samp["latent_shape"][0], samp["vocab_dir"],
                             config["cond_stage_model"]["max_seq_len"])
-  if samp.get("sample_save_progress"):
+  method, args_, kwargs = sampling_call(config, token_ids, args.seed)
+  if method == "ddim_p_sample_loop_progressive":
     # run_ldm_sampler.py:89-94 (with the reference's unpacking bug fixed: three results)
-    _, sample_prog, pred_x0_prog = sampler.ddim_p_sample_loop_progressive(
-        token_ids, samp["latent_shape"], samp["guidance_scale"], seed=args.seed)
+    _, sample_prog, pred_x0_prog = sampler.ddim_p_sample_loop_progressive(*args_, **kwargs)
     for name, t in (("sample_prog.npy", sample_prog), ("pred_x0_prog.npy", pred_x0_prog)):
       print(f"[INFO] Save progressive images to '{name}'...")
       b, r = t.shape[0], t.shape[1]
@@ -130,8 +176,7 @@ def main(argv=None):
       u8 = tensor_to_image(t.reshape(b, r * t.shape[2], t.shape[3], t.shape[4]))
       np.save(name, u8.reshape(tuple(t.shape)))
     return
-  images = sampler.ddim_p_sample_loop(token_ids, samp["latent_shape"], samp["guidance_scale"],
-                                      seed=args.seed)
+  images = getattr(sampler, method)(*args_, **kwargs)
   print(f"[INFO] Save generated images to '{args.out}'...")
   np.save(args.out, tensor_to_image(images))
 
