@@ -207,8 +207,10 @@ int ldm_conv3x3_small(const void* x, int64_t ldx, int in_dtype, const float* ker
 /*
  * GroupNormalization over NHWC (Keras semantics: biased variance over (H,W,C/G)),
  * optionally followed by SiLU.  Two launches:
- *   ldm_groupnorm_partial : per (b, chunk, g) sums  -> partial[B][nchunks][G][2] float
- *   ldm_groupnorm_apply   : finalises mean/rstd, writes (x-mu)*rstd*gamma+beta [silu]
+ *   ldm_groupnorm_partial : per (b, chunk, g) sums of x - K and (x - K)^2 -> partial[B][nchunks][G][2]
+ *                           float, K = x[b, pixel 0, g * C/G] (a shift: the one-pass variance then
+ *                           does not cancel on groups whose mean is large against their spread)
+ *   ldm_groupnorm_apply   : finalises mean/rstd from the same K, writes (x-mu)*rstd*gamma+beta [silu]
  * nchunks is chosen by the caller (ldm_groupnorm_nchunks gives the library's choice).
  * Replaces GroupNormalization(+tf.nn.silu): unet.py:115,137,354,374,377,383,390;
  * autoencoder.py:31,33,68,237,288.

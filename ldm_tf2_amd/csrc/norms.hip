@@ -17,7 +17,15 @@ __host__ __device__ inline GnGeom gn_geom(int C, int epc) {
   return g;
 }
 
-// partial[b][chunk][g][2] = (sum x, sum x^2) over the chunk's pixels and group g
+// Both GroupNorm kernels take the statistics of x - K, K = gn_pilot(): x itself at pixel 0 and the group's
+// first channel.  |mean(x - K)| is then of the order of the group's spread, so the one-pass variance
+// E[(x-K)^2] - E[x-K]^2 does not cancel when the group's mean is large compared with its spread.
+template <typename T>
+__device__ __forceinline__ float gn_pilot(const T* xb, int g, int cpg) {
+  return Elem<T>::ld(xb + (int64_t)g * cpg);
+}
+
+// partial[b][chunk][g][2] = (sum (x-K), sum (x-K)^2) over the chunk's pixels and group g
 template <typename T>
 __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x, int64_t ldx,
                                                          float* __restrict__ partial, int HW, int C,
@@ -33,12 +41,16 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x
   const T* xb = x + (int64_t)b * HW * ldx;
   float* s1 = sm;
   float* s2 = sm + gg.P * C;
+  const int cpg = C / G;
   for (int v0 = 0; v0 < gg.nvec; v0 += gg.VT) {
     const int v = v0 + vl;
     float a1[EPC], a2[EPC];
 #pragma unroll
     for (int e = 0; e < EPC; ++e) { a1[e] = 0.f; a2[e] = 0.f; }
     if (pl < gg.P && v < gg.nvec) {
+      float kk[EPC];
+#pragma unroll
+      for (int e = 0; e < EPC; ++e) kk[e] = gn_pilot(xb, (v * EPC + e) / cpg, cpg);
       // 4 independent 16-byte loads in flight per lane (the kernel is latency-bound otherwise)
       for (int p = p_begin + pl; p < p_end; p += 4 * gg.P) {
         u32x4 c[4];
@@ -50,10 +62,14 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
+          const bool ok = p + u * gg.P < p_end;   // a padded load is 0, and 0 - K is not
           float f[EPC];
           chunk_to_f32(c[u], f, T());
 #pragma unroll
-          for (int e = 0; e < EPC; ++e) { a1[e] += f[e]; a2[e] += f[e] * f[e]; }
+          for (int e = 0; e < EPC; ++e) {
+            const float d = ok ? f[e] - kk[e] : 0.f;
+            a1[e] += d; a2[e] += d * d;
+          }
         }
       }
 #pragma unroll
@@ -66,7 +82,6 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x
   __syncthreads();
   // 8 lanes per group split its (pixel-lane, channel) cells, then a 3-step butterfly
   // (fixed order: deterministic).  G <= 32 groups -> one pass of the 256 threads.
-  const int cpg = C / G;
   for (int g0 = 0; g0 < G; g0 += 32) {
     const int g = g0 + (tid >> 3), sub = tid & 7;
     float t1 = 0.f, t2 = 0.f;
@@ -95,11 +110,12 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
                                                        int C, int G, int nchunks, int achunks,
                                                        float eps, int do_silu) {
   constexpr int EPC = Elem<T>::kPerChunk;
-  __shared__ float s_mean[64], s_rstd[64];
+  __shared__ float s_pilot[64], s_dmean[64], s_rstd[64];
   const GnGeom gg = gn_geom(C, EPC);
   const int tid = threadIdx.x;
   const int chunk = blockIdx.x, b = blockIdx.y;
   const int cpg = C / G;
+  const T* xb = x + (int64_t)b * HW * ldx;
   for (int g0 = 0; g0 < G; g0 += 32) {
     const int g = g0 + (tid >> 3), sub = tid & 7;   // 8 lanes per group over the chunks
     float t1 = 0.f, t2 = 0.f;
@@ -111,11 +127,14 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
 #pragma unroll
     for (int o = 4; o > 0; o >>= 1) { t1 += __shfl_xor(t1, o, 64); t2 += __shfl_xor(t2, o, 64); }
     if (g < G && sub == 0) {
+      // mean = K + dm; apply normalises (x - K) * rstd * gamma + (beta - dm * rstd * gamma), so an offset
+      // far above the spread costs no precision beyond the rounding of x - K itself
       const float n = (float)HW * (float)cpg;
-      const float mean = t1 / n;
-      float var = t2 / n - mean * mean;
+      const float dm = t1 / n;
+      float var = t2 / n - dm * dm;
       var = var < 0.f ? 0.f : var;
-      s_mean[g] = mean;
+      s_pilot[g] = gn_pilot(xb, g, cpg);
+      s_dmean[g] = dm;
       s_rstd[g] = rsqrtf(var + eps);
     }
   }
@@ -123,19 +142,18 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
   const int ppc = (HW + achunks - 1) / achunks;
   const int p_begin = chunk * ppc, p_end = min(HW, p_begin + ppc);
   const int pl = tid / gg.VT, vl = tid - pl * gg.VT;
-  const T* xb = x + (int64_t)b * HW * ldx;
   T* ob = out + (int64_t)b * HW * ldo;
   for (int v0 = 0; v0 < gg.nvec; v0 += gg.VT) {
     const int v = v0 + vl;
     if (!(pl < gg.P && v < gg.nvec)) continue;
-    float mu[EPC], sc[EPC], sh[EPC];
+    float kk[EPC], sc[EPC], sh[EPC];
 #pragma unroll
     for (int e = 0; e < EPC; ++e) {
       const int c = v * EPC + e;
       const int g = c / cpg;
-      mu[e] = s_mean[g];
+      kk[e] = s_pilot[g];
       sc[e] = s_rstd[g] * gamma[c];
-      sh[e] = beta[c];
+      sh[e] = beta[c] - s_dmean[g] * sc[e];
     }
     for (int p = p_begin + pl; p < p_end; p += 4 * gg.P) {
       u32x4 cin[4];
@@ -152,7 +170,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
           chunk_to_f32(cin[u], f, T());
 #pragma unroll
           for (int e = 0; e < EPC; ++e) {
-            float y = (f[e] - mu[e]) * sc[e] + sh[e];
+            float y = (f[e] - kk[e]) * sc[e] + sh[e];
             f[e] = do_silu ? silu_f(y) : y;
           }
           *(u32x4*)(ob + (int64_t)pp * ldo + v * EPC) = f32_to_chunk(f, T());

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """GB/s of the HBM-bound kernels (GroupNorm partial/apply, LayerNorm, attention) on the
-U-Net's shapes at R rows.  Algorithmic bytes = read once + write once."""
+U-Net's shapes at R rows.  Algorithmic bytes = read once + write once.
+--two-launch: only the shapes that take the two-launch GroupNorm (partial sums + apply) by default --
+the KL decoder / encoder at 128^2 and above and the U-Net's 64x64 level at latent 64 -- in f32 and bf16."""
 import argparse
 import os
 import sys
@@ -33,10 +35,34 @@ def time_fn(fn, rounds=5, inner=10):
   return best
 
 
+TWO_LAUNCH_SHAPES = [(1, 256, 256, 128), (1, 256, 256, 256), (1, 128, 128, 512), (1, 512, 512, 128),
+                     (2, 64, 64, 320), (16, 64, 64, 128)]
+
+
+def two_launch(dev):
+  from ldm_tf2_amd._lib import lib
+  print("GroupNorm (partial + apply), default path")
+  for dt in (torch.float32, torch.bfloat16):
+    for B, H, W, C in TWO_LAUNCH_SHAPES:
+      if lib.ldm_groupnorm_fused_supported(B, H * W, C, 32, ops.code(dt)):
+        continue
+      x = torch.randn(B, H, W, C, device=dev).to(dt)
+      g, b = torch.ones(C, device=dev), torch.zeros(C, device=dev)
+      out = torch.empty_like(x)
+      part = torch.empty(B * 128 * 64, device=dev)
+      ms = time_fn(lambda: ops.groupnorm(x, g, b, out, 1e-6, silu=True, partial=part))
+      gbs = 3 * x.numel() * x.element_size() / ms / 1e6
+      print(f"  {str(dt)[6:]:8s} [{B:2d},{H:3d},{W:3d},{C:4d}]  {ms * 1e3:7.1f} us  {gbs:7.0f} GB/s (2 reads + 1 write)")
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument("--rows", type=int, default=32)
+  ap.add_argument("--two-launch", action="store_true")
   args = ap.parse_args()
+  if args.two_launch:
+    two_launch(torch.device("cuda:0"))
+    return
   R, dt, dev = args.rows, torch.bfloat16, torch.device("cuda:0")
   tot = 0.0
   print("LayerNorm")
