@@ -183,6 +183,10 @@ int ldm_gemm_reduce(const ldm_gemm_params* p, void* stream);
  */
 /* 1 if ldm_groupnorm_splitk supports this shape (host query; a subset of ldm_groupnorm_fused's) */
 int ldm_groupnorm_splitk_supported(int B, int HW, int C, int groups, int dtype);
+/* the launch form ldm_groupnorm_splitk runs for this shape (host query, the plan of the launch itself):
+ * form[4] = {GB groups per workgroup, S 16-byte chunks per pixel, NT threads, MAXCH chunks per thread};
+ * LDM_OK, or LDM_ERR_ARG when the shape is not supported (form untouched) */
+int ldm_groupnorm_splitk_form(int B, int HW, int C, int groups, int dtype, int* form);
 int ldm_groupnorm_splitk(const ldm_gemm_params* p, const float* gamma, const float* beta, void* gn_out,
                          int64_t ld_gn, int B, int HW, int groups, float eps, int silu, int store_out,
                          void* stream);

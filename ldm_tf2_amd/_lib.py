@@ -52,6 +52,7 @@ SIGNATURES = {
     "ldm_gemm_splits": (c_i32, [C.POINTER(GemmParams)]),
     "ldm_gemm_reduce": (c_i32, [C.POINTER(GemmParams), c_vp]),
     "ldm_groupnorm_splitk_supported": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "ldm_groupnorm_splitk_form": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i32)]),
     "ldm_groupnorm_splitk": (c_i32, [C.POINTER(GemmParams), c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_f32,
                                      c_i32, c_i32, c_vp]),
     "ldm_conv3x3_small": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32,

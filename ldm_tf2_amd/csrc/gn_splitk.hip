@@ -10,10 +10,22 @@ static bool splitk_plan(int B, int HW, int C, int groups, int esize, GnFusedPlan
   return gn_fused_plan(B, HW, C, groups, esize, pl) && pl->maxch <= 16 && pl->NT <= 512;
 }
 
+// the plan ldm_groupnorm_splitk runs for a shape of this output dtype (false: not supported)
+static bool splitk_shape_plan(int B, int HW, int C, int groups, int dtype, GnFusedPlan* pl) {
+  if (!(dtype == LDM_F32 || dtype == LDM_BF16) || B <= 0 || HW <= 0 || C <= 0 || C % 4) return false;
+  return splitk_plan(B, HW, C, groups, dtype == LDM_BF16 ? 2 : 4, pl);
+}
+
 extern "C" int ldm_groupnorm_splitk_supported(int B, int HW, int C, int groups, int dtype) {
-  if (!(dtype == LDM_F32 || dtype == LDM_BF16) || B <= 0 || HW <= 0 || C <= 0 || C % 4) return 0;
   GnFusedPlan pl;
-  return splitk_plan(B, HW, C, groups, dtype == LDM_BF16 ? 2 : 4, &pl) ? 1 : 0;
+  return splitk_shape_plan(B, HW, C, groups, dtype, &pl) ? 1 : 0;
+}
+
+extern "C" int ldm_groupnorm_splitk_form(int B, int HW, int C, int groups, int dtype, int* form) {
+  GnFusedPlan pl;
+  if (!form || !splitk_shape_plan(B, HW, C, groups, dtype, &pl)) return LDM_ERR_ARG;
+  form[0] = pl.GB; form[1] = pl.S; form[2] = pl.NT; form[3] = pl.maxch;
+  return LDM_OK;
 }
 
 extern "C" int ldm_groupnorm_splitk(const ldm_gemm_params* p, const float* gamma, const float* beta, void* gn_out,
@@ -36,7 +48,7 @@ extern "C" int ldm_groupnorm_splitk(const ldm_gemm_params* p, const float* gamma
                     (!p->addend || (p->add_rows == HW)),
                 "ldm_groupnorm_splitk: alignment (16-byte rows of out / gn_out / residual) or add_rows != HW");
   GnFusedPlan pl;
-  LDM_CHECK_ARG(splitk_plan(B, HW, C, groups, 16 / epc, &pl),
+  LDM_CHECK_ARG(splitk_shape_plan(B, HW, C, groups, p->out_dtype, &pl),
                 "ldm_groupnorm_splitk: shape B=%d HW=%d C=%d groups=%d not supported (ldm_groupnorm_splitk_supported; "
                 "use ldm_gemm_reduce, then a plain GroupNorm)", B, HW, C, groups);
   GnSplitK sk;
