@@ -387,6 +387,34 @@ int ldm_cfg_ddim_update_masked(const float* eps_all, const float* xt, const floa
                                int channels, void* stream);
 
 /*
+ * Classifier-free guidance + PLMS update (pseudo linear multistep, Liu et al. 2022), float32:
+ * the sigma = 0 update of ldm_cfg_ddim_update with eps replaced by an Adams-Bashforth combination of the last
+ * guided eps of THIS loop.  With idx = *index, st = *start (the DDIM index of the loop's first step) and
+ * j = clamp(st - idx, 0, 3) earlier steps:
+ *   e_i = eps_u + s*(eps_c - eps_u)                                  (what the ring stores)
+ *   j=0: e' = e_i                     j=1: e' = (3 e_i - e_{i+1}) / 2
+ *   j=2: e' = (23 e_i - 16 e_{i+1} + 5 e_{i+2}) / 12
+ *   j=3: e' = (55 e_i - 59 e_{i+1} + 37 e_{i+2} - 9 e_{i+3}) / 24   (model_runners.PLMS_WEIGHTS)
+ *   x0 = c1*xt - c2*e'; xt' = sqrt(a_prev)*x0 + sqrt(1 - a_prev)*e'; pred_x0_out (optional) receives x0.
+ * ring = caller-owned [4][B][n] float32: e_i is stored to slot idx & 3 and slots (idx+1 .. idx+j) & 3 are read.
+ * A slot beyond j is NOT read (not multiplied by zero): the ring may start uninitialised or hold another loop's
+ * values.  The slot follows from idx alone, so a captured graph serves any start index.  ring must not alias
+ * any other argument.  coef as in ldm_cfg_ddim_update (its sigma column is not read: PLMS is deterministic);
+ * there is no clip_denoised.  eps_all, xt, xt_out, x_unet_out, dec_index as in ldm_cfg_ddim_update.
+ * Masked blend (z0 != NULL; then mask, q_noise, q_coef are required): exactly that of
+ * ldm_cfg_ddim_update_masked, applied to xt' for idx >= 1 and skipped at idx = 0; the ring and pred_x0_out keep
+ * the unblended step's values.  z0 = NULL: no blend, the five blend arguments are ignored.
+ * Every access is 16 bytes wide: n_per_sample must be a multiple of 4 (true for 4 latent channels) and every
+ * float32 array 16-byte aligned (x_unet_out 8-byte when bf16); other calls are rejected with LDM_ERR_ARG,
+ * there is no scalar path.
+ */
+int ldm_cfg_plms_update(const float* eps_all, const float* xt, float* ring, float* xt_out, float* pred_x0_out,
+                        void* x_unet_out, int x_dtype, const float* coef, int32_t* index, const int32_t* start,
+                        int dec_index, float guidance_scale, int B, int64_t n_per_sample, const float* z0,
+                        const float* mask, const float* q_noise, int64_t q_index_stride, const float* q_coef,
+                        int channels, void* stream);
+
+/*
  * Forward diffusion (model_runners.py:580-600, LatentDiffusionModelTrainer.q_sample):
  *   xt[b] = sqrt_ac[t[b]] * x0[b] + sqrt_1m_ac[t[b]] * noise[b], float32.
  * x0 / noise / xt_out [B][n]; t int32 [B] on the device (DDPM timesteps, clamped to [0, num_steps)); the two

@@ -88,6 +88,8 @@ SIGNATURES = {
                                     c_f32, c_i32, c_i32, c_i64, c_vp]),
     "ldm_cfg_ddim_update_masked": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32,
                                            c_f32, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_vp]),
+    "ldm_cfg_plms_update": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_f32, c_i32,
+                                    c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_vp]),
     "ldm_q_sample": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i64, c_vp]),
     "ldm_post_quant": (c_i32, [c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp]),
     "ldm_groupnorm_fused_supported": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32]),

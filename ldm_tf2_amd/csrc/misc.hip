@@ -336,6 +336,82 @@ __global__ __launch_bounds__(256) void cfg_ddim_kernel(const float* __restrict__
 // of the update kernel has read *index first
 __global__ void dec_index_kernel(int32_t* index) { *index = *index - 1; }
 
+// ---- CFG + PLMS update (+ inpainting blend) -----------------------------------------------
+// The sigma = 0 update above with eps replaced by e', the Adams-Bashforth combination of this step's guided eps
+// and the j = clamp(*start - idx, 0, 3) before it (rows of model_runners.PLMS_WEIGHTS: (1), (3,-1)/2,
+// (23,-16,5)/12, (55,-59,37,-9)/24).  ring [4][B][n]: e_i goes to slot idx & 3, slots (idx+1 .. idx+j) & 3 are
+// read; j is uniform over the launch, so a slot beyond j is never loaded (it may hold NaN).  Four elements per
+// thread, 16-byte accesses (the launcher checks n % 4 and the alignments).  xt_out may be xt.
+__device__ __forceinline__ void st4(float* p, const f32x4& v) { *(f32x4*)p = v; }
+__device__ __forceinline__ void st4(bf16_t* p, const f32x4& v) {
+  u32x2 c;
+  c[0] = pack_bf2(v[0], v[1]);
+  c[1] = pack_bf2(v[2], v[3]);
+  *(u32x2*)p = c;
+}
+
+template <typename TX, bool Blend>
+__global__ __launch_bounds__(256) void cfg_plms_kernel(const float* __restrict__ eps_all, const float* xt,
+                                                       float* __restrict__ ring, float* xt_out,
+                                                       float* __restrict__ pred_x0_out, TX* __restrict__ x_unet,
+                                                       const float* coef, const int32_t* index,
+                                                       const int32_t* start, float gs, int B, int64_t n,
+                                                       BlendArgs bl) {
+  const int idx = *index;
+  const int d = *start - idx;
+  const int j = d < 0 ? 0 : (d > 3 ? 3 : d);
+  const float c1 = coef[idx * 4 + 0], c2 = coef[idx * 4 + 1], a_prev = coef[idx * 4 + 2];
+  const float sa = sqrtf(a_prev);
+  const float sb = sqrtf(1.0f - a_prev);
+  const int64_t total = (int64_t)B * n;
+  float* e_out = ring + (int64_t)(idx & 3) * total;
+  const float* e1 = ring + (int64_t)((idx + 1) & 3) * total;
+  const float* e2 = ring + (int64_t)((idx + 2) & 3) * total;
+  const float* e3 = ring + (int64_t)((idx + 3) & 3) * total;
+  bool blend = false;
+  float qa = 0.f, qb = 0.f;
+  const float* qn = nullptr;
+  if constexpr (Blend) {
+    blend = idx >= 1;                                // never reads a table at -1
+    if (blend) {
+      qa = bl.q_coef[(idx - 1) * 2 + 0];
+      qb = bl.q_coef[(idx - 1) * 2 + 1];
+      qn = bl.q_noise + (int64_t)(idx - 1) * bl.q_stride;
+    }
+  }
+  for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < total; i += (int64_t)gridDim.x * 256 * 4) {
+    const f32x4 eu = *(const f32x4*)(eps_all + i), ec = *(const f32x4*)(eps_all + total + i);
+    const f32x4 x = *(const f32x4*)(xt + i);
+    const f32x4 e0 = eu + gs * (ec - eu);
+    f32x4 ep = e0;
+    if (j == 1) {
+      ep = (3.f * e0 - *(const f32x4*)(e1 + i)) / 2.f;
+    } else if (j == 2) {
+      ep = (23.f * e0 - 16.f * *(const f32x4*)(e1 + i) + 5.f * *(const f32x4*)(e2 + i)) / 12.f;
+    } else if (j == 3) {
+      ep = (55.f * e0 - 59.f * *(const f32x4*)(e1 + i) + 37.f * *(const f32x4*)(e2 + i) -
+            9.f * *(const f32x4*)(e3 + i)) / 24.f;
+    }
+    const f32x4 x0 = c1 * x - c2 * ep;
+    f32x4 o = sa * x0 + sb * ep;
+    if constexpr (Blend) {
+      if (blend) {
+        const f32x4 z = *(const f32x4*)(bl.z0 + i), qe = *(const f32x4*)(qn + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float m = bl.mask[(i + k) / bl.channels];
+          const float q = q_sample_f(qa, qb, z[k], qe[k]);
+          o[k] = m * q + (1.f - m) * o[k];
+        }
+      }
+    }
+    *(f32x4*)(e_out + i) = e0;
+    *(f32x4*)(xt_out + i) = o;
+    if (pred_x0_out) *(f32x4*)(pred_x0_out + i) = x0;
+    if (x_unet) { st4(x_unet + i, o); st4(x_unet + total + i, o); }
+  }
+}
+
 // ---- out[:] = table[i][:], i = *index (pre_decrement: i = --*index first) --------------------------
 // ONE workgroup: the thread that moves the loop counter is in the same workgroup as every reader of it, so the
 // decrement needs no launch of its own, and every later launch of the step sees the new value.
@@ -649,6 +725,53 @@ extern "C" int ldm_cfg_ddim_update_masked(const float* eps_all, const float* xt,
   return cfg_ddim_launch<true>("ldm_cfg_ddim_update_masked", eps_all, xt, noise, noise_index_stride, xt_out,
                                pred_x0_out, x_unet_out, x_dtype, coef, index, dec_index, guidance_scale,
                                clip_denoised, B, n_per_sample, bl, stream);
+}
+
+template <bool Blend>
+static int cfg_plms_launch(const float* eps_all, const float* xt, float* ring, float* xt_out, float* pred_x0_out,
+                           void* x_unet_out, int x_dtype, const float* coef, int32_t* index, const int32_t* start,
+                           int dec_index, float guidance_scale, int B, int64_t n_per_sample, const BlendArgs& bl,
+                           void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  dim3 g(grid_for((int64_t)B * n_per_sample / 4, 256, 1024));
+  if (x_dtype == LDM_BF16)
+    hipLaunchKernelGGL((cfg_plms_kernel<bf16_t, Blend>), g, dim3(256), 0, s, eps_all, xt, ring, xt_out, pred_x0_out,
+                       (bf16_t*)x_unet_out, coef, index, start, guidance_scale, B, n_per_sample, bl);
+  else
+    hipLaunchKernelGGL((cfg_plms_kernel<float, Blend>), g, dim3(256), 0, s, eps_all, xt, ring, xt_out, pred_x0_out,
+                       (float*)x_unet_out, coef, index, start, guidance_scale, B, n_per_sample, bl);
+  int st = ldm_launch_status("ldm_cfg_plms_update");
+  if (st != LDM_OK) return st;
+  if (dec_index) {
+    hipLaunchKernelGGL(dec_index_kernel, dim3(1), dim3(1), 0, s, index);
+    st = ldm_launch_status("ldm_cfg_plms_update");
+  }
+  return st;
+}
+
+extern "C" int ldm_cfg_plms_update(const float* eps_all, const float* xt, float* ring, float* xt_out,
+                                   float* pred_x0_out, void* x_unet_out, int x_dtype, const float* coef,
+                                   int32_t* index, const int32_t* start, int dec_index, float guidance_scale, int B,
+                                   int64_t n_per_sample, const float* z0, const float* mask, const float* q_noise,
+                                   int64_t q_index_stride, const float* q_coef, int channels, void* stream) {
+  LDM_CHECK_ARG(eps_all && xt && ring && xt_out && coef && index && start, "ldm_cfg_plms_update: null pointer");
+  LDM_CHECK_ARG(DT_OK(x_dtype) && B > 0 && n_per_sample > 0 && n_per_sample % 4 == 0,
+                "ldm_cfg_plms_update: bad args (n_per_sample=%lld must be a positive multiple of 4)",
+                (long long)n_per_sample);
+  const uintptr_t al = (uintptr_t)eps_all | (uintptr_t)xt | (uintptr_t)ring | (uintptr_t)xt_out |
+                       (uintptr_t)pred_x0_out | (uintptr_t)z0 | (uintptr_t)q_noise;
+  LDM_CHECK_ARG(al % 16 == 0 && (uintptr_t)x_unet_out % (x_dtype == LDM_BF16 ? 8 : 16) == 0 &&
+                    (!z0 || q_index_stride % 4 == 0),
+                "ldm_cfg_plms_update: arrays must be 16-byte aligned (q_index_stride a multiple of 4)");
+  if (!z0)
+    return cfg_plms_launch<false>(eps_all, xt, ring, xt_out, pred_x0_out, x_unet_out, x_dtype, coef, index, start,
+                                  dec_index, guidance_scale, B, n_per_sample, BlendArgs{}, stream);
+  LDM_CHECK_ARG(mask && q_noise && q_coef, "ldm_cfg_plms_update: z0 without mask / q_noise / q_coef");
+  LDM_CHECK_ARG(channels > 0 && n_per_sample % channels == 0 && q_index_stride >= 0,
+                "ldm_cfg_plms_update: bad args (n_per_sample=%lld, channels=%d)", (long long)n_per_sample, channels);
+  const BlendArgs bl{z0, mask, q_noise, q_index_stride, q_coef, channels};
+  return cfg_plms_launch<true>(eps_all, xt, ring, xt_out, pred_x0_out, x_unet_out, x_dtype, coef, index, start,
+                               dec_index, guidance_scale, B, n_per_sample, bl, stream);
 }
 
 extern "C" int ldm_q_sample(const float* x0, const float* noise, int64_t noise_index_stride, const int32_t* index,

@@ -18,6 +18,9 @@ img2img / inpainting run the same step from an intermediat
 index: the start latent is the forward diffusion (q_sample, the reference trainer's
 :580-600) of the encoded init image, and a mask pins kept latent cells to it inside the
 step's one update launch.
+
+sampler="plms"  swaps that update for the PLMS one: the same launch count, a ring of the last
+four guided eps and the loop's start index on the device, the same captured graph for any start index.
 """
 from __future__ import annotations
 
@@ -217,10 +220,27 @@ class LatentDiffusionModel(object):
     return outputs
 
 
+# PLMS: row j = Adams-Bashforth weights of (e_i, e_{i+1}, .., e_{i+j}), the guided eps of the
+# step at DDIM index i and of the j steps before it in the loop.  cfg_plms_kernel (csrc/misc.hip) carries the same
+# numbers as (numerators) / denominator.
+PLMS_WEIGHTS = (
+    (1.,),
+    (3. / 2., -1. / 2.),
+    (23. / 12., -16. / 12., 5. / 12.),
+    (55. / 24., -59. / 24., 37. / 24., -9. / 24.),
+)
+SAMPLERS = ("ddim", "plms")
+
+
 class LatentDiffusionModelSampler(LatentDiffusionModel):
 
-  def __init__(self, *args, use_graph=True, verbose=True, temb_table=True, **kwargs):
+  def __init__(self, *args, use_graph=True, verbose=True, temb_table=True, sampler="ddim", **kwargs):
     super().__init__(*args, **kwargs)
+    if sampler not in SAMPLERS:
+      raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
+    if sampler == "plms" and self._eta != 0:
+      raise ValueError(f"sampler='plms' is deterministic: eta must be 0, got {self._eta}")
+    self._sampler = sampler
     self._use_graph = use_graph
     self._use_temb_table = bool(temb_table)      # A/B: False = four temb launches + a decrement launch per step
     self._temb_tbl = None
@@ -255,8 +275,18 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       self._xt = torch.empty(B, h, w, c, dtype=f32, device=dev)
       self._x2 = torch.empty(2 * B, h, w, c, dtype=f32, device=dev)
       self._eps = torch.empty(2 * B, h, w, c, dtype=f32, device=dev)
+      if self._sampler == "plms":
+        # the last four guided eps by DDIM index & 3 (never initialised: a step reads only slots its own loop wrote)
+        # and the DDIM index of the loop's first step
+        self._ring = torch.empty(4, B, h, w, c, dtype=f32, device=dev)
+        self._start = torch.zeros(1, dtype=torch.int32, device=dev)
       self._state_key = key
       self._graph = None
+
+  def _set_loop_start(self, start_index):
+    """PLMS: the loop's first step is the one at DDIM index `start_index` (it has no history)."""
+    if self._sampler == "plms":
+      self._start.fill_(int(start_index))
 
   def _owned(self, name, src, shape, dtype=torch.float32):
     """`src` copied into a buffer the sampler owns (one per name and shape): a captured graph reads it at a
@@ -284,6 +314,17 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     # selects the step's row of the temb table), so a loop starts from index = N and ends at 0.
     self._unet.forward(self._x2, steps=self._steps_dev, index=self._index_dev, out=self._eps, paired_rows=True,
                        **self._temb_kwargs(dec_index))
+    if self._sampler == "plms":
+      # (eta = 0: no noise table; the loops never clip)
+      assert noise_table is None and not clip_denoised
+      blend = {}
+      if masked:
+        blend = dict(z0=self._z0_buf, mask=self._mask_buf, q_noise=self._q_buf, q_coef=self._device_q_tables()[2],
+                     q_index_stride=self._q_buf[0].numel())
+      ops.cfg_plms_update(self._eps, self._xt, self._xt, self._ring, self._coef_dev, self._index_dev, self._start,
+                          guidance_scale, x_unet_out=self._x2, dec_index=dec_index and not self._pre_dec,
+                          pred_x0_out=pred_x0_out, **blend)
+      return
     stride = 0 if noise_table is None else noise_table[0].numel()
     if masked:
       ops.cfg_ddim_update_masked(self._eps, self._xt, self._xt, self._coef_dev, self._index_dev, guidance_scale,
@@ -300,7 +341,8 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
   def ddim_sample(self, xt, cond, index, guidance_scale=1., clip_denoised=True,
                   return_pred_x0=False, noise=None):
     """model_runners.py:438-472 for a host-side `index`.  `noise` [B,h,w,c] replaces
-    the reference's tf.random.normal draw (zeros when omitted; irrelevant at eta=0)."""
+    the reference's tf.random.normal draw (zeros when omitted; irrelevant at eta=0).
+    Always the DDIM step, also on a sampler="plms" sampler: a single step has no history."""
     xt = torch.as_tensor(xt, dtype=torch.float32).to(self.device).contiguous()
     B, h, w, c = xt.shape
     self._alloc_state(B, h, w, c)
@@ -405,8 +447,9 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       self._x2[:B].copy_(xt)
       self._x2[B:].copy_(xt)
       self._index_dev.fill_(self._loop_start_index(n))                    # :476 (index = N - 1 in the first step)
+      self._set_loop_start(n - 1)
 
-    gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, False)
+    gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, False, self._sampler)
     self._sample_loop(n, reset, lambda dec: self._step(guidance_scale, False, noise_table, dec_index=dec),
                       gkey, record)
     return self._finish(self._xt)
@@ -470,8 +513,9 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     def reset():
       ops.q_sample(z0_buf, q_buf[k - 1], t_start, sa, sb, self._xt, x_unet_out=self._x2)
       self._index_dev.fill_(self._loop_start_index(k))
+      self._set_loop_start(k - 1)
 
-    gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, masked)
+    gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, masked, self._sampler)
     self._sample_loop(k, reset, lambda dec: self._step(guidance_scale, False, noise_table, dec_index=dec,
                                                         masked=masked), gkey, record)
     return self._finish(self._xt)
@@ -502,6 +546,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     self._x2[:B].copy_(xt)
     self._x2[B:].copy_(xt)
     self._index_dev.fill_(self._loop_start_index(n))
+    self._set_loop_start(n - 1)
     sample_prog = torch.zeros(B, num_records, h, w, c, dtype=torch.float32, device=self.device)
     x0_prog = torch.zeros_like(sample_prog)
     pred_x0 = torch.empty_like(self._xt)

@@ -19,7 +19,7 @@ from ._lib import ACT_GEGLU, ACT_GELU, ACT_NONE, ACT_SILU, BF16, F32, GemmParams
 __all__ = [
     "ACT_NONE", "ACT_GELU", "ACT_GEGLU", "ACT_SILU", "F32", "BF16", "code", "linear", "conv3x3",
     "bmm_nt", "conv3x3_small", "groupnorm", "layernorm", "softmax_rows", "attention",
-    "time_embedding", "gemv", "cfg_ddim_update", "cfg_ddim_update_masked", "q_sample", "post_quant", "vq_nearest", "embedding",
+    "time_embedding", "gemv", "cfg_ddim_update", "cfg_ddim_update_masked", "cfg_plms_update", "q_sample", "post_quant", "vq_nearest", "embedding",
     "minmax_u8", "cast",
 ]
 
@@ -821,6 +821,32 @@ def cfg_ddim_update_masked(eps_all, xt, xt_out, coef, index, guidance_scale, z0,
       _ptr(_f32(coef, "coef")), _ptr(index), int(bool(dec_index)), float(guidance_scale), int(bool(clip_denoised)),
       B, n, _ptr(_f32(z0, "z0")), _ptr(_f32(mask, "mask")), _ptr(_f32(q_noise, "q_noise")), int(q_index_stride),
       _ptr(_f32(q_coef, "q_coef")), c, _stream()), "ldm_cfg_ddim_update_masked")
+  return xt_out
+
+
+def cfg_plms_update(eps_all, xt, xt_out, ring, coef, index, start, guidance_scale, x_unet_out=None, dec_index=False,
+                    pred_x0_out=None, z0=None, mask=None, q_noise=None, q_coef=None, q_index_stride=0):
+  """CFG + PLMS update (include/ldm_hip.h): the sigma = 0 update of cfg_ddim_update with eps replaced by the
+  Adams-Bashforth combination of this step's guided eps and the min(*start - *index, 3) before it.  ring
+  [4,B,...] float32 (slot *index & 3 is written, the next j slots are read), start int32 [1] on the device.
+  `z0` (with mask [B,h,w], q_noise, q_coef [N,2]): the inpainting blend of cfg_ddim_update_masked, same launch."""
+  B = xt.shape[0]
+  n = xt.numel() // B
+  c = xt.shape[-1]
+  assert ring.is_contiguous() and ring.numel() == 4 * xt.numel()
+  assert index.dtype == torch.int32 and start.dtype == torch.int32
+  if z0 is not None:
+    assert z0.is_contiguous() and z0.numel() == xt.numel()
+    assert mask.is_contiguous() and mask.numel() * c == xt.numel()
+    assert q_noise.is_contiguous() and q_coef.is_contiguous() and q_coef.shape == (coef.shape[0], 2)
+    assert q_noise.numel() >= (q_coef.shape[0] - 1) * q_index_stride + xt.numel()
+  xd = code(x_unet_out.dtype) if x_unet_out is not None else F32
+  check(lib.ldm_cfg_plms_update(
+      _ptr(_f32(eps_all, "eps_all")), _ptr(_f32(xt, "xt")), _ptr(_f32(ring, "ring")), _ptr(_f32(xt_out, "xt_out")),
+      _ptr(_f32(pred_x0_out, "pred_x0_out")), _ptr(x_unet_out), xd, _ptr(_f32(coef, "coef")), _ptr(index),
+      _ptr(start), int(bool(dec_index)), float(guidance_scale), B, n, _ptr(_f32(z0, "z0")),
+      _ptr(_f32(mask, "mask")), _ptr(_f32(q_noise, "q_noise")), int(q_index_stride), _ptr(_f32(q_coef, "q_coef")),
+      c, _stream()), "ldm_cfg_plms_update")
   return xt_out
 
 

@@ -21,6 +21,9 @@ img2img / inpainting: optional `ldm_sampling` keys `init_image` (a .npy of uint8
 [B,H,W,3], read as x/127.5 - 1), `strength` (default 0.75) and `mask` (a .npy [H,W] or
 [B,H,W], nonzero = keep; needs `init_image`).  With `init_image` the autoencoder is built
 or loaded with its encoder.  Without these keys nothing changes.
+
+Solver: optional `ldm_sampling` key `sampler`, `ddim` (default) or `plms` (pseudo linear multistep, needs
+`ldm.eta` 0); every loop above honours it.
 """
 from __future__ import annotations
 
@@ -87,6 +90,11 @@ def downsampling_factor(config):
   return 2 ** (len(mult) - 1)
 
 
+def sampler_name(config):
+  """`ldm_sampling.sampler`: "ddim" (default; the reference's YAML has no such key) or "plms" (DESIGN.md section 8)."""
+  return config["ldm_sampling"].get("sampler", "ddim")
+
+
 def sampling_call(config, token_ids, seed):
   """(sampler method name, positional args, kwargs) of the call main() makes for `config`."""
   samp = config["ldm_sampling"]
@@ -147,7 +155,8 @@ def build_from_config(config, dtype=torch.bfloat16, device="cuda:0", seed=2, use
                                 weights=_load_weights(ck.get("autoencoder"), "autoencoder"),
                                 with_encoder=with_encoder or None)
   return LatentDiffusionModelSampler(unet=unet, autoencoder=autoencoder, cond_stage_model=transformer,
-                                     use_graph=use_graph, verbose=verbose, **config["ldm"])
+                                     use_graph=use_graph, verbose=verbose, sampler=sampler_name(config),
+                                     **config["ldm"])
 
 
 def main(argv=None):
