@@ -428,6 +428,58 @@ int ldm_q_sample(const float* x0, const float* noise, int64_t noise_index_stride
                  int num_steps, float* xt_out, void* x_unet_out, int x_dtype, int B, int64_t n_per_sample,
                  void* stream);
 
+/*
+ * Sampling noise drawn on the device.  Generator: Philox4x32-10 (Salmon et al., SC'11).
+ * rng = uint32[4] on the device, {seed & 0xffffffff, seed >> 32, first_sample_index, 0}: the first two words are
+ * the key, read through the pointer by every kernel below (a new seed or shard offset changes no kernel argument).
+ * The words of elements 4q .. 4q+3 of sample b ([h][w][c] flattened) in stream s are Philox of the counter
+ * (q, first_sample_index + b, s, 0).  Word x -> u = ((x >> 8) + 0.5) * 2^-24; the four normals are
+ * r0 cos(2 pi u1), r0 sin(2 pi u1), r2 cos(2 pi u3), r2 sin(2 pi u3) with r = sqrt(-2 ln u): |z| <= 5.887.
+ * Stream words (model_runners.XT_STREAM, ETA_STREAM, ENCODE_STREAM, Q_STREAM): x_T; eta noise of DDIM index i at
+ * ETA + i; the posterior noise of get_latents; forward-diffusion noise Q[i] at Q + i.  Disjoint for i < 2^29.
+ * Every access is 16 bytes wide: n_per_sample must be a multiple of 4 and every float32 / uint32 array 16-byte
+ * aligned (x_unet_out 8-byte when bf16); other calls are rejected with LDM_ERR_ARG, there is no scalar path.
+ */
+#define LDM_RNG_XT_STREAM 0u
+#define LDM_RNG_ETA_STREAM (1u << 29)
+#define LDM_RNG_ENCODE_STREAM (1u << 30)
+#define LDM_RNG_Q_STREAM ((1u << 30) + 1u)
+
+/* out [B][n] uint32 = the raw Philox words of stream `stream_word` (the integer part of the generator, exact). */
+int ldm_philox_u32(uint32_t* out, const uint32_t* rng, uint32_t stream_word, int B, int64_t n_per_sample,
+                   void* stream);
+
+/* out [B][n] float32 = the normals of stream `stream_word`; x_unet_out (optional, dtype x_dtype) receives
+ * concat([out, out]).  x_T (LDM_RNG_XT_STREAM, with the first U-Net input), the posterior noise of get_latents
+ * (LDM_RNG_ENCODE_STREAM), and one row of a noise table the entries above can read. */
+int ldm_normal_fill(float* out, const uint32_t* rng, uint32_t stream_word, int B, int64_t n_per_sample,
+                    void* x_unet_out, int x_dtype, void* stream);
+
+/* ldm_q_sample with `noise` = the normals of stream `stream_word` (a host value: LDM_RNG_Q_STREAM + k - 1 for the
+ * start latent of an img2img loop at DDIM index k - 1), drawn in the kernel.  Other arguments as in ldm_q_sample. */
+int ldm_q_sample_rng(const float* x0, const uint32_t* rng, uint32_t stream_word, const int32_t* t,
+                     const float* sqrt_alphas_cumprod, const float* sqrt_one_minus_alphas_cumprod, int num_steps,
+                     float* xt_out, void* x_unet_out, int x_dtype, int B, int64_t n_per_sample, void* stream);
+
+/*
+ * ldm_cfg_ddim_update and ldm_cfg_ddim_update_masked behind one entry, without their tables: with idx = *index,
+ * `noise` is the normals of stream LDM_RNG_ETA_STREAM + idx (not drawn when sigma = coef[idx][3] is 0) and the
+ * blend's Q[idx - 1] those of stream LDM_RNG_Q_STREAM + idx - 1 (nothing is drawn at idx = 0), both formed in
+ * registers by the one launch.  z0 = NULL: no blend, mask / q_coef / channels are ignored.  clip_denoised,
+ * pred_x0_out, x_unet_out and dec_index as in ldm_cfg_ddim_update; same arithmetic, four elements per thread.
+ */
+int ldm_cfg_ddim_update_rng(const float* eps_all, const float* xt, const uint32_t* rng, float* xt_out,
+                            float* pred_x0_out, void* x_unet_out, int x_dtype, const float* coef, int32_t* index,
+                            int dec_index, float guidance_scale, int clip_denoised, int B, int64_t n_per_sample,
+                            const float* z0, const float* mask, const float* q_coef, int channels, void* stream);
+
+/* ldm_cfg_plms_update with the blend's Q[idx - 1] drawn like that (PLMS has no eta noise); z0 = NULL: no blend,
+ * nothing is drawn.  The ring rules are those of ldm_cfg_plms_update. */
+int ldm_cfg_plms_update_rng(const float* eps_all, const float* xt, float* ring, float* xt_out, float* pred_x0_out,
+                            void* x_unet_out, int x_dtype, const float* coef, int32_t* index, const int32_t* start,
+                            const uint32_t* rng, int dec_index, float guidance_scale, int B, int64_t n_per_sample,
+                            const float* z0, const float* mask, const float* q_coef, int channels, void* stream);
+
 /* decode_first_stage prologue (model_runners.py:426 + autoencoder.py:362,434):
  * out = Dense_{C->C}(latents / scale_factor), C <= 8; float32 in, out_dtype out. */
 int ldm_post_quant(const float* latents, float scale_factor, const float* kernel_io,

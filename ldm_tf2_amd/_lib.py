@@ -19,6 +19,7 @@ ACT_NONE, ACT_GELU, ACT_GEGLU, ACT_SILU = 0, 1, 2, 3
 OK, ERR_ARG, ERR_LAUNCH, ERR_WORKSPACE = 0, -1, -2, -3     # include/ldm_hip.h status codes
 
 c_i64, c_i32, c_f32, c_vp, c_sz = C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_size_t
+c_u32 = C.c_uint32
 
 
 class GemmParams(C.Structure):
@@ -91,6 +92,13 @@ SIGNATURES = {
     "ldm_cfg_plms_update": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_f32, c_i32,
                                     c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_vp]),
     "ldm_q_sample": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i64, c_vp]),
+    "ldm_philox_u32": (c_i32, [c_vp, c_vp, c_u32, c_i32, c_i64, c_vp]),
+    "ldm_normal_fill": (c_i32, [c_vp, c_vp, c_u32, c_i32, c_i64, c_vp, c_i32, c_vp]),
+    "ldm_q_sample_rng": (c_i32, [c_vp, c_vp, c_u32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i64, c_vp]),
+    "ldm_cfg_ddim_update_rng": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_f32, c_i32,
+                                        c_i32, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "ldm_cfg_plms_update_rng": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
+                                        c_f32, c_i32, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "ldm_post_quant": (c_i32, [c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp]),
     "ldm_groupnorm_fused_supported": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32]),
     "ldm_groupnorm_fused": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_f32,

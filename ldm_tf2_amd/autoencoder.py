@@ -253,9 +253,11 @@ class _Encoder(_Blocks):
     self._ws = ops.new_workspace(dev)
     self.max_chunk = 16
 
-  def encode(self, images):
+  def encode(self, images, max_chunk=None):
     """images f32 [B,H,W,3] -> quant_conv(Encoder(images)) f32 [B,H/f,W/f,zc]; chunked over the
-    batch like `_Decoder.decode`."""
+    batch like `_Decoder.decode`.  `max_chunk` (default: the encoder's own) bounds the images per pass;
+    1 = every image on its own, so its latents do not depend on the batch it arrived in (the launch
+    plans of a pass depend on its row count)."""
     assert images.dtype == torch.float32 and images.is_contiguous()
     B, H, W, _ = images.shape
     f = 2 ** sum(1 for blk in self.down if blk[0] == "down")
@@ -266,7 +268,7 @@ class _Encoder(_Blocks):
         hh, ww = hh // 2, ww // 2
       else:
         per = max(per, hh * ww * max(blk[1].cin, blk[1].cout))
-    n = _chunk_rows(B, per, self.dtype, self.max_chunk)
+    n = _chunk_rows(B, per, self.dtype, max_chunk or self.max_chunk)
     with ops.workspace_scope(self._ws):
       for i in range(0, B, n):
         i0 = min(i, B - n)
@@ -347,12 +349,12 @@ class _AutoencoderBase:
     self._decoder = _Decoder(weights, dtype, self.device, attention_resolutions)
     self._encoder = _Encoder(weights, dtype, self.device, attention_resolutions) if with_encoder else None
 
-  def _encode(self, inputs):
+  def _encode(self, inputs, per_sample=False):
     if self._encoder is None:
       raise RuntimeError("this autoencoder was built without its encoder: pass with_encoder=True "
                          "(or weights that contain encoder/*)")
     x = torch.as_tensor(inputs, dtype=torch.float32).to(self.device).contiguous()
-    return self._encoder.encode(x)
+    return self._encoder.encode(x, max_chunk=1 if per_sample else None)
 
 
 class AutoencoderKL(_AutoencoderBase):
@@ -374,9 +376,10 @@ class AutoencoderKL(_AutoencoderBase):
                      multipliers=self._multipliers, attention_resolutions=(), image_size=image_size,
                      double_z=True))
 
-  def encode(self, inputs, training=False):
-    """autoencoder.py:353-359: images [B,H,W,3] -> DiagonalGaussian posterior."""
-    return DiagonalGaussian(self._encode(inputs))
+  def encode(self, inputs, training=False, per_sample=False):
+    """autoencoder.py:353-359: images [B,H,W,3] -> DiagonalGaussian posterior.  `per_sample`: one encoder pass
+    per image, so an image's moments are the same bits in any batch."""
+    return DiagonalGaussian(self._encode(inputs, per_sample))
 
   def decode(self, inputs, training=False, scale_factor=1.0):
     """autoencoder.py:361-364."""
@@ -418,9 +421,10 @@ class AutoencoderVQ(_AutoencoderBase):
                      image_size=image_size or latent_size * 2 ** (len(self._multipliers) - 1),
                      double_z=False))
 
-  def encode(self, inputs, only_encode=False, training=False):
-    """autoencoder.py:411-419: latents, or (quantized latents, codebook_loss, indices)."""
-    z = self._encode(inputs)
+  def encode(self, inputs, only_encode=False, training=False, per_sample=False):
+    """autoencoder.py:411-419: latents, or (quantized latents, codebook_loss, indices).  `per_sample` as in
+    AutoencoderKL.encode."""
+    z = self._encode(inputs, per_sample)
     if only_encode:
       return z
     q = torch.empty_like(z)

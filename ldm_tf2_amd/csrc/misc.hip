@@ -412,6 +412,177 @@ __global__ __launch_bounds__(256) void cfg_plms_kernel(const float* __restrict__
   }
 }
 
+// ---- sampling noise drawn in the kernels ------------------------------------------------
+// Philox4x32-10 (Salmon et al., SC'11): counter (c0..c3), key (k0, k1) -> four 32-bit words.  Plain integer code.
+__device__ __forceinline__ u32x4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                               uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  u32x4 o = {c0, c1, c2, c3};
+  return o;
+}
+
+// rng = {seed_lo, seed_hi, first_sample_index, 0} on the device.  The words of elements 4q .. 4q+3 of sample b in
+// stream `s`: key (seed_lo, seed_hi), counter (q, first_sample_index + b, s, 0).
+__device__ __forceinline__ u32x4 rng_words(const uint32_t* __restrict__ rng, uint32_t q, uint32_t b, uint32_t s) {
+  return philox4x32_10(q, rng[2] + b, s, 0u, rng[0], rng[1]);
+}
+
+// u = ((x >> 8) + 0.5) * 2^-24 in one rounding: never 0; above 1/2 the half is rounded to even.
+__device__ __forceinline__ float rng_uniform(uint32_t x) { return fmaf((float)(x >> 8), 0x1p-24f, 0x1p-25f); }
+
+// Box-Muller on the word pairs (x0, x1) and (x2, x3): the normals of elements 4q .. 4q+3.
+__device__ __forceinline__ f32x4 rng_normal4(const uint32_t* __restrict__ rng, uint32_t q, uint32_t b, uint32_t s) {
+  const u32x4 w = rng_words(rng, q, b, s);
+  const float r0 = sqrtf(-2.0f * logf(rng_uniform(w[0]))), r1 = sqrtf(-2.0f * logf(rng_uniform(w[2])));
+  float s0, c0, s1, c1;
+  sincospif(2.0f * rng_uniform(w[1]), &s0, &c0);
+  sincospif(2.0f * rng_uniform(w[3]), &s1, &c1);
+  f32x4 z = {r0 * c0, r0 * s0, r1 * c1, r1 * s1};
+  return z;
+}
+
+__global__ __launch_bounds__(256) void philox_u32_kernel(uint32_t* __restrict__ out, const uint32_t* __restrict__ rng,
+                                                         uint32_t stream_word, int B, int64_t n) {
+  const int64_t total = (int64_t)B * n;
+  for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < total; i += (int64_t)gridDim.x * 256 * 4) {
+    const int64_t b = i / n;
+    *(u32x4*)(out + i) = rng_words(rng, (uint32_t)((i - b * n) >> 2), (uint32_t)b, stream_word);
+  }
+}
+
+template <typename TX>
+__global__ __launch_bounds__(256) void normal_fill_kernel(float* __restrict__ out, const uint32_t* __restrict__ rng,
+                                                          uint32_t stream_word, int B, int64_t n,
+                                                          TX* __restrict__ x_unet) {
+  const int64_t total = (int64_t)B * n;
+  for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < total; i += (int64_t)gridDim.x * 256 * 4) {
+    const int64_t b = i / n;
+    const f32x4 z = rng_normal4(rng, (uint32_t)((i - b * n) >> 2), (uint32_t)b, stream_word);
+    *(f32x4*)(out + i) = z;
+    if (x_unet) { st4(x_unet + i, z); st4(x_unet + total + i, z); }
+  }
+}
+
+// ldm_q_sample with the noise of stream `stream_word` drawn here.
+template <typename TX>
+__global__ __launch_bounds__(256) void q_sample_rng_kernel(const float* __restrict__ x0,
+                                                           const uint32_t* __restrict__ rng, uint32_t stream_word,
+                                                           const int32_t* __restrict__ t,
+                                                           const float* __restrict__ sqrt_ac,
+                                                           const float* __restrict__ sqrt_1m_ac, int num_steps,
+                                                           float* __restrict__ xt_out, TX* __restrict__ x_unet, int B,
+                                                           int64_t n) {
+  const int64_t total = (int64_t)B * n;
+  for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < total; i += (int64_t)gridDim.x * 256 * 4) {
+    const int64_t b = i / n;
+    int ti = t[b];
+    ti = ti < 0 ? 0 : (ti >= num_steps ? num_steps - 1 : ti);      // (a stray t reads a valid row)
+    const float sa = sqrt_ac[ti], sb = sqrt_1m_ac[ti];
+    const f32x4 x = *(const f32x4*)(x0 + i);
+    const f32x4 z = rng_normal4(rng, (uint32_t)((i - b * n) >> 2), (uint32_t)b, stream_word);
+    f32x4 o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = q_sample_f(sa, sb, x[k], z[k]);
+    *(f32x4*)(xt_out + i) = o;
+    if (x_unet) { st4(x_unet + i, o); st4(x_unet + total + i, o); }
+  }
+}
+
+// cfg_ddim_kernel (Plms = false) and cfg_plms_kernel (Plms = true) with their tables drawn here: the eta noise of
+// stream eta_stream + idx (DDIM, skipped when sigma == 0: uniform over the launch) and the blend's Q[idx-1] of
+// stream q_stream + idx - 1 (bl.z0 != NULL and idx >= 1; nothing is drawn at idx = 0).  bl.q_noise is not read.
+// Four elements per thread, the arithmetic of the table kernels expression for expression.
+template <typename TX, bool Plms>
+__global__ __launch_bounds__(256) void cfg_update_rng_kernel(const float* __restrict__ eps_all, const float* xt,
+                                                             float* __restrict__ ring, float* xt_out,
+                                                             float* __restrict__ pred_x0_out, TX* __restrict__ x_unet,
+                                                             const float* coef, const int32_t* index,
+                                                             const int32_t* start, const uint32_t* __restrict__ rng,
+                                                             uint32_t eta_stream, uint32_t q_stream, float gs,
+                                                             int clip, int B, int64_t n, BlendArgs bl) {
+  const int idx = *index;
+  int j = 0;
+  if constexpr (Plms) {
+    const int d = *start - idx;
+    j = d < 0 ? 0 : (d > 3 ? 3 : d);
+  }
+  const float c1 = coef[idx * 4 + 0], c2 = coef[idx * 4 + 1], a_prev = coef[idx * 4 + 2];
+  const float sigma = Plms ? 0.f : coef[idx * 4 + 3];
+  const float sa = sqrtf(a_prev);
+  const float sb = Plms ? sqrtf(1.0f - a_prev) : sqrtf(1.0f - a_prev - sigma * sigma);
+  const int64_t total = (int64_t)B * n;
+  float* e_out = nullptr;
+  const float *e1 = nullptr, *e2 = nullptr, *e3 = nullptr;
+  if constexpr (Plms) {
+    e_out = ring + (int64_t)(idx & 3) * total;
+    e1 = ring + (int64_t)((idx + 1) & 3) * total;
+    e2 = ring + (int64_t)((idx + 2) & 3) * total;
+    e3 = ring + (int64_t)((idx + 3) & 3) * total;
+  }
+  const bool blend = bl.z0 != nullptr && idx >= 1;   // never draws a row at -1
+  float qa = 0.f, qb = 0.f;
+  if (blend) {
+    qa = bl.q_coef[(idx - 1) * 2 + 0];
+    qb = bl.q_coef[(idx - 1) * 2 + 1];
+  }
+  const bool draw_eta = !Plms && sigma != 0.f;
+  for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < total; i += (int64_t)gridDim.x * 256 * 4) {
+    const f32x4 eu = *(const f32x4*)(eps_all + i), ec = *(const f32x4*)(eps_all + total + i);
+    const f32x4 x = *(const f32x4*)(xt + i);
+    const f32x4 e0 = eu + gs * (ec - eu);
+    f32x4 ep = e0;
+    if constexpr (Plms) {
+      if (j == 1) {
+        ep = (3.f * e0 - *(const f32x4*)(e1 + i)) / 2.f;
+      } else if (j == 2) {
+        ep = (23.f * e0 - 16.f * *(const f32x4*)(e1 + i) + 5.f * *(const f32x4*)(e2 + i)) / 12.f;
+      } else if (j == 3) {
+        ep = (55.f * e0 - 59.f * *(const f32x4*)(e1 + i) + 37.f * *(const f32x4*)(e2 + i) -
+              9.f * *(const f32x4*)(e3 + i)) / 24.f;
+      }
+    }
+    f32x4 x0 = c1 * x - c2 * ep;
+    if constexpr (!Plms) {
+      if (clip) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x0[k] = fminf(fmaxf(x0[k], -1.f), 1.f);
+      }
+    }
+    f32x4 o = sa * x0 + sb * ep;
+    const int64_t b = i / n;
+    const uint32_t q = (uint32_t)((i - b * n) >> 2);
+    if (draw_eta) {
+      const f32x4 nz = rng_normal4(rng, q, (uint32_t)b, eta_stream + (uint32_t)idx);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[k] = o[k] + nz[k] * sigma;
+    }
+    if (blend) {
+      const f32x4 z = *(const f32x4*)(bl.z0 + i);
+      const f32x4 qe = rng_normal4(rng, q, (uint32_t)b, q_stream + (uint32_t)(idx - 1));
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float m = bl.mask[(i + k) / bl.channels];
+        const float qs = q_sample_f(qa, qb, z[k], qe[k]);
+        o[k] = m * qs + (1.f - m) * o[k];
+      }
+    }
+    if constexpr (Plms) *(f32x4*)(e_out + i) = e0;
+    *(f32x4*)(xt_out + i) = o;
+    if (pred_x0_out) *(f32x4*)(pred_x0_out + i) = x0;
+    if (x_unet) { st4(x_unet + i, o); st4(x_unet + total + i, o); }
+  }
+}
+
 // ---- out[:] = table[i][:], i = *index (pre_decrement: i = --*index first) --------------------------
 // ONE workgroup: the thread that moves the loop counter is in the same workgroup as every reader of it, so the
 // decrement needs no launch of its own, and every later launch of the step sees the new value.
@@ -794,6 +965,122 @@ extern "C" int ldm_q_sample(const float* x0, const float* noise, int64_t noise_i
                        B, n_per_sample);
   return ldm_launch_status("ldm_q_sample");
 }
+
+#define AL16(p) (((uintptr_t)(p) % 16) == 0)
+#define XU_OK(p, d) (((uintptr_t)(p) % ((d) == LDM_BF16 ? 8 : 16)) == 0)
+
+extern "C" int ldm_philox_u32(uint32_t* out, const uint32_t* rng, uint32_t stream_word, int B, int64_t n_per_sample,
+                              void* stream) {
+  LDM_CHECK_ARG(out && rng, "ldm_philox_u32: null pointer");
+  LDM_CHECK_ARG(B > 0 && n_per_sample > 0 && n_per_sample % 4 == 0 && AL16(out),
+                "ldm_philox_u32: n_per_sample=%lld must be a positive multiple of 4, out 16-byte aligned",
+                (long long)n_per_sample);
+  dim3 g(grid_for((int64_t)B * n_per_sample / 4, 256, 1024));
+  hipLaunchKernelGGL(philox_u32_kernel, g, dim3(256), 0, (hipStream_t)stream, out, rng, stream_word, B, n_per_sample);
+  return ldm_launch_status("ldm_philox_u32");
+}
+
+extern "C" int ldm_normal_fill(float* out, const uint32_t* rng, uint32_t stream_word, int B, int64_t n_per_sample,
+                               void* x_unet_out, int x_dtype, void* stream) {
+  LDM_CHECK_ARG(out && rng, "ldm_normal_fill: null pointer");
+  LDM_CHECK_ARG(DT_OK(x_dtype) && B > 0 && n_per_sample > 0 && n_per_sample % 4 == 0 && AL16(out) &&
+                    XU_OK(x_unet_out, x_dtype),
+                "ldm_normal_fill: n_per_sample=%lld must be a positive multiple of 4, arrays 16-byte aligned",
+                (long long)n_per_sample);
+  hipStream_t s = (hipStream_t)stream;
+  dim3 g(grid_for((int64_t)B * n_per_sample / 4, 256, 1024));
+  if (x_dtype == LDM_BF16)
+    hipLaunchKernelGGL(normal_fill_kernel<bf16_t>, g, dim3(256), 0, s, out, rng, stream_word, B, n_per_sample,
+                       (bf16_t*)x_unet_out);
+  else
+    hipLaunchKernelGGL(normal_fill_kernel<float>, g, dim3(256), 0, s, out, rng, stream_word, B, n_per_sample,
+                       (float*)x_unet_out);
+  return ldm_launch_status("ldm_normal_fill");
+}
+
+extern "C" int ldm_q_sample_rng(const float* x0, const uint32_t* rng, uint32_t stream_word, const int32_t* t,
+                                const float* sqrt_alphas_cumprod, const float* sqrt_one_minus_alphas_cumprod,
+                                int num_steps, float* xt_out, void* x_unet_out, int x_dtype, int B,
+                                int64_t n_per_sample, void* stream) {
+  LDM_CHECK_ARG(x0 && rng && t && sqrt_alphas_cumprod && sqrt_one_minus_alphas_cumprod && xt_out,
+                "ldm_q_sample_rng: null pointer");
+  LDM_CHECK_ARG(DT_OK(x_dtype) && B > 0 && n_per_sample > 0 && num_steps > 0 && n_per_sample % 4 == 0 && AL16(x0) &&
+                    AL16(xt_out) && XU_OK(x_unet_out, x_dtype),
+                "ldm_q_sample_rng: n_per_sample=%lld must be a positive multiple of 4, arrays 16-byte aligned",
+                (long long)n_per_sample);
+  hipStream_t s = (hipStream_t)stream;
+  dim3 g(grid_for((int64_t)B * n_per_sample / 4, 256, 1024));
+  if (x_dtype == LDM_BF16)
+    hipLaunchKernelGGL(q_sample_rng_kernel<bf16_t>, g, dim3(256), 0, s, x0, rng, stream_word, t, sqrt_alphas_cumprod,
+                       sqrt_one_minus_alphas_cumprod, num_steps, xt_out, (bf16_t*)x_unet_out, B, n_per_sample);
+  else
+    hipLaunchKernelGGL(q_sample_rng_kernel<float>, g, dim3(256), 0, s, x0, rng, stream_word, t, sqrt_alphas_cumprod,
+                       sqrt_one_minus_alphas_cumprod, num_steps, xt_out, (float*)x_unet_out, B, n_per_sample);
+  return ldm_launch_status("ldm_q_sample_rng");
+}
+
+// checks and launch shared by ldm_cfg_ddim_update_rng (ring = start = NULL) and ldm_cfg_plms_update_rng
+static int cfg_update_rng_launch(const char* what, bool plms, const float* eps_all, const float* xt, float* ring,
+                                 float* xt_out, float* pred_x0_out, void* x_unet_out, int x_dtype, const float* coef,
+                                 int32_t* index, const int32_t* start, const uint32_t* rng, int dec_index,
+                                 float guidance_scale, int clip_denoised, int B, int64_t n_per_sample, const float* z0,
+                                 const float* mask, const float* q_coef, int channels, void* stream) {
+  LDM_CHECK_ARG(eps_all && xt && xt_out && coef && index && rng && (!plms || (ring && start)), "%s: null pointer",
+                what);
+  LDM_CHECK_ARG(DT_OK(x_dtype) && B > 0 && n_per_sample > 0 && n_per_sample % 4 == 0,
+                "%s: bad args (n_per_sample=%lld must be a positive multiple of 4)", what, (long long)n_per_sample);
+  LDM_CHECK_ARG(AL16(eps_all) && AL16(xt) && AL16(ring) && AL16(xt_out) && AL16(pred_x0_out) && AL16(z0) &&
+                    XU_OK(x_unet_out, x_dtype),
+                "%s: arrays must be 16-byte aligned", what);
+  BlendArgs bl{};
+  if (z0) {
+    LDM_CHECK_ARG(mask && q_coef, "%s: z0 without mask / q_coef", what);
+    LDM_CHECK_ARG(channels > 0 && n_per_sample % channels == 0, "%s: bad args (n_per_sample=%lld, channels=%d)", what,
+                  (long long)n_per_sample, channels);
+    bl = BlendArgs{z0, mask, nullptr, 0, q_coef, channels};
+  }
+  hipStream_t s = (hipStream_t)stream;
+  dim3 g(grid_for((int64_t)B * n_per_sample / 4, 256, 1024));
+#define LAUNCH_RNG(TX, PLMS)                                                                                        \
+  hipLaunchKernelGGL((cfg_update_rng_kernel<TX, PLMS>), g, dim3(256), 0, s, eps_all, xt, ring, xt_out, pred_x0_out, \
+                     (TX*)x_unet_out, coef, index, start, rng, (uint32_t)LDM_RNG_ETA_STREAM,                       \
+                     (uint32_t)LDM_RNG_Q_STREAM, guidance_scale, clip_denoised, B, n_per_sample, bl)
+  if (plms) {
+    if (x_dtype == LDM_BF16) LAUNCH_RNG(bf16_t, true); else LAUNCH_RNG(float, true);
+  } else {
+    if (x_dtype == LDM_BF16) LAUNCH_RNG(bf16_t, false); else LAUNCH_RNG(float, false);
+  }
+#undef LAUNCH_RNG
+  int st = ldm_launch_status(what);
+  if (st != LDM_OK) return st;
+  if (dec_index) {
+    hipLaunchKernelGGL(dec_index_kernel, dim3(1), dim3(1), 0, s, index);
+    st = ldm_launch_status(what);
+  }
+  return st;
+}
+
+extern "C" int ldm_cfg_ddim_update_rng(const float* eps_all, const float* xt, const uint32_t* rng, float* xt_out,
+                                       float* pred_x0_out, void* x_unet_out, int x_dtype, const float* coef,
+                                       int32_t* index, int dec_index, float guidance_scale, int clip_denoised, int B,
+                                       int64_t n_per_sample, const float* z0, const float* mask, const float* q_coef,
+                                       int channels, void* stream) {
+  return cfg_update_rng_launch("ldm_cfg_ddim_update_rng", false, eps_all, xt, nullptr, xt_out, pred_x0_out, x_unet_out,
+                               x_dtype, coef, index, nullptr, rng, dec_index, guidance_scale, clip_denoised, B,
+                               n_per_sample, z0, mask, q_coef, channels, stream);
+}
+
+extern "C" int ldm_cfg_plms_update_rng(const float* eps_all, const float* xt, float* ring, float* xt_out,
+                                       float* pred_x0_out, void* x_unet_out, int x_dtype, const float* coef,
+                                       int32_t* index, const int32_t* start, const uint32_t* rng, int dec_index,
+                                       float guidance_scale, int B, int64_t n_per_sample, const float* z0,
+                                       const float* mask, const float* q_coef, int channels, void* stream) {
+  return cfg_update_rng_launch("ldm_cfg_plms_update_rng", true, eps_all, xt, ring, xt_out, pred_x0_out, x_unet_out,
+                               x_dtype, coef, index, start, rng, dec_index, guidance_scale, 0, B, n_per_sample, z0,
+                               mask, q_coef, channels, stream);
+}
+#undef AL16
+#undef XU_OK
 
 extern "C" int ldm_select_row(const float* table, int64_t ld, int rows, int cols, int32_t* index, int pre_decrement,
                               float* out, void* stream) {

@@ -21,6 +21,10 @@ step's one update launch.
 
 sampler="plms"  swaps that update for the PLMS one: the same launch count, a ring of the last
 four guided eps and the loop's start index on the device, the same captured graph for any start index.
+
+noise_source="device"  draws every random number of the loops on the device: Philox4x32-10 keyed
+by the seed, counted by (element, global sample index, stream), formed in registers inside the step's update launch.
+No noise table is built or uploaded, and one captured graph serves any seed.
 """
 from __future__ import annotations
 
@@ -63,6 +67,11 @@ def normal_latents(seed, first_index, count, shape_hwc, stream=None):
 
 ENCODE_STREAM = 1 << 30          # posterior noise E of get_latents
 Q_STREAM = (1 << 30) + 1         # + i: forward-diffusion noise Q[i] of DDIM index i
+# noise_source="device" only (the host draws key x_T and the eta noise by the seed word, see normal_latents): the
+# stream word is the third counter word of the device generator; the four ranges are disjoint for i < 2^29.
+XT_STREAM = 0                    # x_T
+ETA_STREAM = 1 << 29             # + i: eta noise of the step at DDIM index i
+NOISE_SOURCES = ("host", "device")
 
 
 def img2img_start(strength, num_ddim_steps):
@@ -138,6 +147,18 @@ class LatentDiffusionModel(object):
     self.device = getattr(unet, "device", torch.device("cuda:0"))
     self._tables = None
     self._q_tables = None
+    self._noise_source = "host"
+    self._rng = None
+
+  def _set_rng(self, seed, first_sample_index):
+    """The device generator's state uint32[4] = {seed_lo, seed_hi, first_sample_index, 0} (seed mod 2^64; int32
+    storage), allocated on first use and rewritten in place: the kernels read it through a fixed pointer."""
+    seed = int(seed) % (1 << 64)
+    words = np.array([seed & 0xffffffff, seed >> 32, int(first_sample_index) % (1 << 32), 0], dtype=np.uint32)
+    if self._rng is None:
+      self._rng = torch.zeros(4, dtype=torch.int32, device=self.device)
+    self._rng.copy_(torch.from_numpy(words.view(np.int32)))
+    return self._rng
 
   def _device_tables(self):
     """Device copies of the schedule, made on first use: per DDIM index the row
@@ -175,13 +196,19 @@ class LatentDiffusionModel(object):
 
   def get_latents(self, inputs, noise=None, seed=0, first_sample_index=0):
     """model_runners.py:602-625: images [B,H,W,3] in [-1, 1] -> scale_factor * latents.  KL: a posterior
-    sample (`noise` [B,h,w,c], else drawn from `seed`'s ENCODE_STREAM per global sample index, where the
-    reference draws an unseeded tf.random.normal); VQ: encode(only_encode=True)."""
+    sample (`noise` [B,h,w,c], else drawn from `seed`'s ENCODE_STREAM per global sample index -- by
+    ldm_normal_fill when the noise source is "device" -- where the reference draws an unseeded tf.random.normal); VQ: encode(only_encode=True)."""
+    # noise source "device": sample i must not depend on how samples are spread over launches or GPUs, so every
+    # image is encoded on its own (a pass's launch plans depend on its batch); "host": one pass, as before
+    enc = dict(per_sample=True) if self._noise_source == "device" else {}
     if isinstance(self._autoencoder, AutoencoderKL):
-      posterior = self._autoencoder.encode(inputs)
+      posterior = self._autoencoder.encode(inputs, **enc)
       moments = posterior._moments
       B, h, w, c2 = moments.shape
-      if noise is None:
+      if noise is None and self._noise_source == "device":
+        noise = ops.normal_fill(torch.empty(B, h, w, c2 // 2, dtype=torch.float32, device=moments.device),
+                                self._set_rng(seed, first_sample_index), ENCODE_STREAM)
+      elif noise is None:
         noise = normal_latents(seed, first_sample_index, B, (h, w, c2 // 2), stream=ENCODE_STREAM)
       noise = torch.as_tensor(np.asarray(noise) if not isinstance(noise, torch.Tensor) else noise,
                               dtype=torch.float32).to(self.device).contiguous()
@@ -191,7 +218,7 @@ class LatentDiffusionModel(object):
       # (mean + std * noise) * scale_factor: the sample, then the float32 scale (:624)
       return ops.gaussian_sample(moments, out, noise=noise, out_scale=np.float32(self._scale_factor))
     elif isinstance(self._autoencoder, AutoencoderVQ):
-      latents = self._autoencoder.encode(inputs, only_encode=True)
+      latents = self._autoencoder.encode(inputs, only_encode=True, **enc)
       return latents * np.float32(self._scale_factor)
     raise NotImplementedError("Invalid autoencoder")
 
@@ -234,10 +261,14 @@ SAMPLERS = ("ddim", "plms")
 
 class LatentDiffusionModelSampler(LatentDiffusionModel):
 
-  def __init__(self, *args, use_graph=True, verbose=True, temb_table=True, sampler="ddim", **kwargs):
+  def __init__(self, *args, use_graph=True, verbose=True, temb_table=True, sampler="ddim", noise_source="host",
+               **kwargs):
     super().__init__(*args, **kwargs)
     if sampler not in SAMPLERS:
       raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
+    if noise_source not in NOISE_SOURCES:
+      raise ValueError(f"noise_source must be one of {NOISE_SOURCES}, got {noise_source!r}")
+    self._noise_source = noise_source
     if sampler == "plms" and self._eta != 0:
       raise ValueError(f"sampler='plms' is deterministic: eta must be 0, got {self._eta}")
     self._sampler = sampler
@@ -280,6 +311,8 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
         # and the DDIM index of the loop's first step
         self._ring = torch.empty(4, B, h, w, c, dtype=f32, device=dev)
         self._start = torch.zeros(1, dtype=torch.int32, device=dev)
+      if self._noise_source == "device" and self._rng is None:
+        self._rng = torch.zeros(4, dtype=torch.int32, device=dev)    # (written by each loop's reset)
       self._state_key = key
       self._graph = None
 
@@ -306,14 +339,31 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     """Per-step noise in a buffer the sampler owns (one per shape)."""
     return self._owned("_noise_buf", noises, shape)
 
-  def _step(self, guidance_scale, clip_denoised, noise_table, dec_index, pred_x0_out=None, masked=False):
+  def _step(self, guidance_scale, clip_denoised, noise_table, dec_index, pred_x0_out=None, masked=False, rng=False):
     """unet([xt; xt], t=steps[index]) -> CFG -> DDIM update, all on device.  `masked`: the update also pins the
-    kept cells for the next step (img2img inpainting: _z0_buf, _mask_buf, _q_buf; still one launch)."""
+    kept cells for the next step (img2img inpainting: _z0_buf, _mask_buf, _q_buf; still one launch).  `rng`: the
+    update draws the eta noise and the blend's Q itself from _rng (no noise_table, no _q_buf; still one launch)."""
     # (paired_rows: x2 = [xt; xt], one timestep -- rows r and r + B differ only in their context, :449-452)
     # The loop counter moves at the START of a step (`dec_index`: the U-Net's first launch pre-decrements it and
     # selects the step's row of the temb table), so a loop starts from index = N and ends at 0.
     self._unet.forward(self._x2, steps=self._steps_dev, index=self._index_dev, out=self._eps, paired_rows=True,
                        **self._temb_kwargs(dec_index))
+    if rng:
+      assert noise_table is None
+      blend = {}
+      if masked:
+        blend = dict(z0=self._z0_buf, mask=self._mask_buf, q_coef=self._device_q_tables()[2])
+      dec = dec_index and not self._pre_dec
+      if self._sampler == "plms":
+        assert not clip_denoised
+        ops.cfg_plms_update_rng(self._eps, self._xt, self._xt, self._ring, self._coef_dev, self._index_dev,
+                                self._start, self._rng, guidance_scale, x_unet_out=self._x2, dec_index=dec,
+                                pred_x0_out=pred_x0_out, **blend)
+      else:
+        ops.cfg_ddim_update_rng(self._eps, self._xt, self._xt, self._coef_dev, self._index_dev, self._rng,
+                                guidance_scale, x_unet_out=self._x2, dec_index=dec, clip_denoised=clip_denoised,
+                                pred_x0_out=pred_x0_out, **blend)
+      return
     if self._sampler == "plms":
       # (eta = 0: no noise table; the loops never clip)
       assert noise_table is None and not clip_denoised
@@ -375,13 +425,34 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     self._ctx_shape = tuple(cond.shape)
 
   def _eta_noise_table(self, noises, seed, first_sample_index, B, h, w, c):
-    """[N,B,h,w,c] per-step noise (read only when eta > 0): `noises`, else per DDIM index i the stream seed + 1 + i."""
+    """[N,B,h,w,c] per-step noise (read only when eta > 0): `noises`, else per DDIM index i the stream seed + 1 + i
+    (noise source "device": row i filled on the device from stream ETA_STREAM + i)."""
     if self._eta == 0.:
       return None
     n = len(self._ddim_steps)
+    if noises is None and self._noise_source == "device":
+      return self._device_table("_noise_buf", (n, B, h, w, c), ETA_STREAM, n, seed, first_sample_index)
     if noises is None:
       noises = np.stack([normal_latents(seed + 1 + i, first_sample_index, B, (h, w, c)) for i in range(n)])
     return self._noise_table(noises, (n, B, h, w, c))
+
+  def _device_table(self, name, shape, stream0, rows, seed, first_sample_index):
+    """A per-step table the caller did not give while giving another (the step then runs the table entry): rows
+    0 .. rows-1 of the owned buffer `name` filled by ldm_normal_fill from streams stream0 + i, the numbers the fused
+    path would draw; later rows are never read."""
+    buf = getattr(self, name, None)
+    if buf is None or tuple(buf.shape) != tuple(shape):
+      buf = torch.zeros(shape, dtype=torch.float32, device=self.device)
+      setattr(self, name, buf)
+      self._graph = None
+    rng = self._set_rng(seed, first_sample_index)
+    for i in range(rows):
+      ops.normal_fill(buf[i], rng, stream0 + i)
+    return buf
+
+  def _draws_on_device(self, noises, q_noises=None):
+    """Noise source "device" and no per-step table given: the step's update launch draws what it needs."""
+    return self._noise_source == "device" and noises is None and q_noises is None
 
   def _sample_loop(self, num_steps, reset, step, gkey, record):
     """Run `num_steps` DDIM steps from the state `reset()` sets (latents, U-Net input and the device counter at
@@ -427,32 +498,53 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     """model_runners.py:474-509.  Extra inputs the reference lacks: `x_T` [B,h,w,4]
     (else N(0,1) from `seed`, keyed per global sample index), `noises` [N,B,h,w,4]
     indexed by DDIM index (only read when eta > 0), `record` (list: receives x_t
-    after every step -- disables graph replay)."""
+    after every step -- disables graph replay).  noise_source="device": what the caller
+    does not give is drawn on the device; without `noises` no table exists."""
     B, h, w, c = (int(s) for s in shape)
     context = self._cond_stage_model(cond_model_inputs)                   # :475
     n = len(self._ddim_steps)
+    xt = self._x_T(x_T, seed, first_sample_index, B, h, w, c)
+    # :480-482 concat(context[:4], context[4:]) == context
+    cond_combined = context
+    self._alloc_state(B, h, w, c)
+    self._set_context(cond_combined)
+    rng = self._draws_on_device(noises)
+    noise_table = None if rng else self._eta_noise_table(noises, seed, first_sample_index, B, h, w, c)
+
+    def reset():
+      self._set_x_T(xt, seed, first_sample_index, B)
+      self._index_dev.fill_(self._loop_start_index(n))                    # :476 (index = N - 1 in the first step)
+      self._set_loop_start(n - 1)
+
+    gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, False, self._noise_source, rng,
+            self._sampler)
+    self._sample_loop(n, reset, lambda dec: self._step(guidance_scale, False, noise_table, dec_index=dec, rng=rng),
+                      gkey, record)
+    return self._finish(self._xt)
+
+  def _x_T(self, x_T, seed, first_sample_index, B, h, w, c):
+    """The caller's x_T on the device; drawn on the host when omitted; None (noise source "device") = drawn on the
+    device by _set_x_T."""
+    if x_T is None and self._noise_source == "device":
+      return None
     if x_T is None:
       x_T = normal_latents(seed, first_sample_index, B, (h, w, c))
     xt = torch.as_tensor(np.asarray(x_T) if not isinstance(x_T, torch.Tensor) else x_T,
                          dtype=torch.float32).to(self.device).contiguous()
     assert tuple(xt.shape) == (B, h, w, c)
-    # :480-482 concat(context[:4], context[4:]) == context
-    cond_combined = context
-    self._alloc_state(B, h, w, c)
-    self._set_context(cond_combined)
-    noise_table = self._eta_noise_table(noises, seed, first_sample_index, B, h, w, c)
+    return xt
 
-    def reset():
-      self._xt.copy_(xt)
-      self._x2[:B].copy_(xt)
-      self._x2[B:].copy_(xt)
-      self._index_dev.fill_(self._loop_start_index(n))                    # :476 (index = N - 1 in the first step)
-      self._set_loop_start(n - 1)
-
-    gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, False, self._sampler)
-    self._sample_loop(n, reset, lambda dec: self._step(guidance_scale, False, noise_table, dec_index=dec),
-                      gkey, record)
-    return self._finish(self._xt)
+  def _set_x_T(self, xt, seed, first_sample_index, B):
+    """The loop's start state: the latents and both halves of the first U-Net input; with the noise source
+    "device" also the generator state (and x_T itself from stream XT_STREAM when the caller gave none)."""
+    if self._noise_source == "device":
+      self._set_rng(seed, first_sample_index)
+    if xt is None:
+      ops.normal_fill(self._xt, self._rng, XT_STREAM, x_unet_out=self._x2)
+      return
+    self._xt.copy_(xt)
+    self._x2[:B].copy_(xt)
+    self._x2[B:].copy_(xt)
 
   def _finish(self, latents):
     if self._verbose:                                                     # :503
@@ -497,12 +589,18 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
                        f"got {tuple(mask.shape)}")
     self._alloc_state(B, h, w, c)
     self._set_context(context)
-    noise_table = self._eta_noise_table(noises, seed, first_sample_index, B, h, w, c)
-    if q_noises is None:
-      q_noises = np.zeros((n, B, h, w, c), dtype=np.float32)
-      for i in range(k):                       # (rows >= k are never read)
-        q_noises[i] = normal_latents(seed, first_sample_index, B, (h, w, c), stream=Q_STREAM + i)
-    q_buf = self._owned("_q_buf", q_noises, (n, B, h, w, c))
+    rng = self._draws_on_device(noises, q_noises)
+    noise_table = None if rng else self._eta_noise_table(noises, seed, first_sample_index, B, h, w, c)
+    if rng:
+      q_buf = None                             # (Q is drawn where it is used: reset's q_sample and the blend)
+    elif q_noises is None and self._noise_source == "device":
+      q_buf = self._device_table("_q_buf", (n, B, h, w, c), Q_STREAM, k, seed, first_sample_index)
+    else:
+      if q_noises is None:
+        q_noises = np.zeros((n, B, h, w, c), dtype=np.float32)
+        for i in range(k):                     # (rows >= k are never read)
+          q_noises[i] = normal_latents(seed, first_sample_index, B, (h, w, c), stream=Q_STREAM + i)
+      q_buf = self._owned("_q_buf", q_noises, (n, B, h, w, c))
     z0_buf = self._owned("_z0_buf", z0, (B, h, w, c))
     if mask is not None:
       self._owned("_mask_buf", mask, (B, h, w))
@@ -511,13 +609,19 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     masked = mask is not None
 
     def reset():
-      ops.q_sample(z0_buf, q_buf[k - 1], t_start, sa, sb, self._xt, x_unet_out=self._x2)
+      if self._noise_source == "device":
+        self._set_rng(seed, first_sample_index)
+      if rng:
+        ops.q_sample_rng(z0_buf, self._rng, Q_STREAM + k - 1, t_start, sa, sb, self._xt, x_unet_out=self._x2)
+      else:
+        ops.q_sample(z0_buf, q_buf[k - 1], t_start, sa, sb, self._xt, x_unet_out=self._x2)
       self._index_dev.fill_(self._loop_start_index(k))
       self._set_loop_start(k - 1)
 
-    gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, masked, self._sampler)
+    gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, masked, self._noise_source, rng,
+            self._sampler)
     self._sample_loop(k, reset, lambda dec: self._step(guidance_scale, False, noise_table, dec_index=dec,
-                                                        masked=masked), gkey, record)
+                                                        masked=masked, rng=rng), gkey, record)
     return self._finish(self._xt)
 
   def ddim_p_sample_loop_progressive(self, cond_model_inputs, shape, guidance_scale=5.,
@@ -535,23 +639,19 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     context = self._cond_stage_model(cond_model_inputs)
     n = len(self._ddim_steps)
     num_records = n // record_freq
-    if x_T is None:
-      x_T = normal_latents(seed, first_sample_index, B, (h, w, c))
-    xt = torch.as_tensor(np.asarray(x_T) if not isinstance(x_T, torch.Tensor) else x_T,
-                         dtype=torch.float32).to(self.device).contiguous()
+    xt = self._x_T(x_T, seed, first_sample_index, B, h, w, c)
     self._alloc_state(B, h, w, c)
     self._set_context(context)
-    noise_table = self._eta_noise_table(noises, seed, first_sample_index, B, h, w, c)
-    self._xt.copy_(xt)
-    self._x2[:B].copy_(xt)
-    self._x2[B:].copy_(xt)
+    rng = self._draws_on_device(noises)
+    noise_table = None if rng else self._eta_noise_table(noises, seed, first_sample_index, B, h, w, c)
+    self._set_x_T(xt, seed, first_sample_index, B)
     self._index_dev.fill_(self._loop_start_index(n))
     self._set_loop_start(n - 1)
     sample_prog = torch.zeros(B, num_records, h, w, c, dtype=torch.float32, device=self.device)
     x0_prog = torch.zeros_like(sample_prog)
     pred_x0 = torch.empty_like(self._xt)
     for index in range(n - 1, -1, -1):
-      self._step(guidance_scale, False, noise_table, dec_index=True, pred_x0_out=pred_x0)
+      self._step(guidance_scale, False, noise_table, dec_index=True, pred_x0_out=pred_x0, rng=rng)
       r = index // record_freq
       if r < num_records:                      # later (smaller) indices overwrite the slot
         sample_prog[:, r].copy_(self._xt)

@@ -19,7 +19,8 @@ from ._lib import ACT_GEGLU, ACT_GELU, ACT_NONE, ACT_SILU, BF16, F32, GemmParams
 __all__ = [
     "ACT_NONE", "ACT_GELU", "ACT_GEGLU", "ACT_SILU", "F32", "BF16", "code", "linear", "conv3x3",
     "bmm_nt", "conv3x3_small", "groupnorm", "layernorm", "softmax_rows", "attention",
-    "time_embedding", "gemv", "cfg_ddim_update", "cfg_ddim_update_masked", "cfg_plms_update", "q_sample", "post_quant", "vq_nearest", "embedding",
+    "time_embedding", "gemv", "cfg_ddim_update", "cfg_ddim_update_masked", "cfg_plms_update", "q_sample",
+    "philox_u32", "normal_fill", "q_sample_rng", "cfg_ddim_update_rng", "cfg_plms_update_rng", "post_quant", "vq_nearest", "embedding",
     "minmax_u8", "cast",
 ]
 
@@ -869,6 +870,91 @@ def q_sample(x0, noise, t, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, x
                          sqrt_alphas_cumprod.numel(), _ptr(_f32(xt_out, "xt_out")), _ptr(x_unet_out), xd, B, n,
                          _stream()), "ldm_q_sample")
   return xt_out
+
+
+def _rng(rng):
+  """The generator state of include/ldm_hip.h: four 32-bit words on the device (int32 storage holds uint32 bits)."""
+  assert rng.dtype == torch.int32 and rng.is_contiguous() and rng.numel() == 4
+  return _ptr(rng)
+
+
+def philox_u32(out, rng, stream_word):
+  """out [B,...] int32 storage = the raw Philox4x32-10 words of one stream (include/ldm_hip.h)."""
+  B = out.shape[0]
+  assert out.dtype == torch.int32 and out.is_contiguous()
+  check(lib.ldm_philox_u32(_ptr(out), _rng(rng), int(stream_word) & 0xffffffff, B, out.numel() // B, _stream()),
+        "ldm_philox_u32")
+  return out
+
+
+def normal_fill(out, rng, stream_word, x_unet_out=None):
+  """out [B,...] float32 = the N(0,1) draws of one stream, keyed per global sample index; x_unet_out: [out; out]
+  in its own dtype."""
+  B = out.shape[0]
+  assert out.is_contiguous()
+  assert x_unet_out is None or (x_unet_out.is_contiguous() and x_unet_out.numel() == 2 * out.numel())
+  xd = code(x_unet_out.dtype) if x_unet_out is not None else F32
+  check(lib.ldm_normal_fill(_ptr(_f32(out, "out")), _rng(rng), int(stream_word) & 0xffffffff, B, out.numel() // B,
+                            _ptr(x_unet_out), xd, _stream()), "ldm_normal_fill")
+  return out
+
+
+def q_sample_rng(x0, rng, stream_word, t, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod, xt_out, x_unet_out=None):
+  """q_sample with its noise drawn in the kernel from stream `stream_word` (a host int)."""
+  B = x0.shape[0]
+  n = x0.numel() // B
+  assert x0.is_contiguous() and xt_out.is_contiguous() and xt_out.numel() == x0.numel()
+  assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == B
+  assert sqrt_alphas_cumprod.numel() == sqrt_one_minus_alphas_cumprod.numel()
+  assert x_unet_out is None or (x_unet_out.is_contiguous() and x_unet_out.numel() == 2 * x0.numel())
+  xd = code(x_unet_out.dtype) if x_unet_out is not None else F32
+  check(lib.ldm_q_sample_rng(_ptr(_f32(x0, "x0")), _rng(rng), int(stream_word) & 0xffffffff, _ptr(t),
+                             _ptr(_f32(sqrt_alphas_cumprod, "sqrt_alphas_cumprod")),
+                             _ptr(_f32(sqrt_one_minus_alphas_cumprod, "sqrt_one_minus_alphas_cumprod")),
+                             sqrt_alphas_cumprod.numel(), _ptr(_f32(xt_out, "xt_out")), _ptr(x_unet_out), xd, B, n,
+                             _stream()), "ldm_q_sample_rng")
+  return xt_out
+
+
+def _blend_rng(xt, coef, z0, mask, q_coef):
+  if z0 is not None:
+    assert z0.is_contiguous() and z0.numel() == xt.numel()
+    assert mask.is_contiguous() and mask.numel() * xt.shape[-1] == xt.numel()
+    assert q_coef.is_contiguous() and q_coef.shape == (coef.shape[0], 2)
+
+
+def cfg_ddim_update_rng(eps_all, xt, xt_out, coef, index, rng, guidance_scale, x_unet_out=None, dec_index=False,
+                        clip_denoised=False, pred_x0_out=None, z0=None, mask=None, q_coef=None):
+  """cfg_ddim_update / cfg_ddim_update_masked (`z0`, mask [B,h,w], q_coef [N,2]) with the eta noise and the blend's
+  Q drawn in the launch from `rng` (streams ETA_STREAM + *index, Q_STREAM + *index - 1): no tables."""
+  B = xt.shape[0]
+  n = xt.numel() // B
+  _blend_rng(xt, coef, z0, mask, q_coef)
+  xd = code(x_unet_out.dtype) if x_unet_out is not None else F32
+  check(lib.ldm_cfg_ddim_update_rng(
+      _ptr(_f32(eps_all, "eps_all")), _ptr(_f32(xt, "xt")), _rng(rng), _ptr(_f32(xt_out, "xt_out")),
+      _ptr(_f32(pred_x0_out, "pred_x0_out")), _ptr(x_unet_out), xd, _ptr(_f32(coef, "coef")), _ptr(index),
+      int(bool(dec_index)), float(guidance_scale), int(bool(clip_denoised)), B, n, _ptr(_f32(z0, "z0")),
+      _ptr(_f32(mask, "mask")), _ptr(_f32(q_coef, "q_coef")), xt.shape[-1], _stream()), "ldm_cfg_ddim_update_rng")
+  return xt_out
+
+
+def cfg_plms_update_rng(eps_all, xt, xt_out, ring, coef, index, start, rng, guidance_scale, x_unet_out=None,
+                        dec_index=False, pred_x0_out=None, z0=None, mask=None, q_coef=None):
+  """cfg_plms_update with the blend's Q drawn in the launch from `rng` (stream Q_STREAM + *index - 1)."""
+  B = xt.shape[0]
+  n = xt.numel() // B
+  assert ring.is_contiguous() and ring.numel() == 4 * xt.numel()
+  assert index.dtype == torch.int32 and start.dtype == torch.int32
+  _blend_rng(xt, coef, z0, mask, q_coef)
+  xd = code(x_unet_out.dtype) if x_unet_out is not None else F32
+  check(lib.ldm_cfg_plms_update_rng(
+      _ptr(_f32(eps_all, "eps_all")), _ptr(_f32(xt, "xt")), _ptr(_f32(ring, "ring")), _ptr(_f32(xt_out, "xt_out")),
+      _ptr(_f32(pred_x0_out, "pred_x0_out")), _ptr(x_unet_out), xd, _ptr(_f32(coef, "coef")), _ptr(index),
+      _ptr(start), _rng(rng), int(bool(dec_index)), float(guidance_scale), B, n, _ptr(_f32(z0, "z0")),
+      _ptr(_f32(mask, "mask")), _ptr(_f32(q_coef, "q_coef")), xt.shape[-1], _stream()), "ldm_cfg_plms_update_rng")
+  return xt_out
+
 
 def post_quant(latents, scale_factor, kernel_io, bias, out):
   Cc = latents.shape[-1]

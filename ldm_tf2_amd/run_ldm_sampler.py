@@ -24,6 +24,10 @@ or loaded with its encoder.  Without these keys nothing changes.
 
 Solver: optional `ldm_sampling` key `sampler`, `ddim` (default) or `plms` (pseudo linear multistep, needs
 `ldm.eta` 0); every loop above honours it.
+
+Noise: optional `ldm_sampling` key `noise_source`, `host` (default: NumPy generators, tables uploaded before the loop)
+or `device` (Philox streams drawn inside the update launches, no tables).  The two sources draw
+different numbers from the same `--seed`.
 """
 from __future__ import annotations
 
@@ -95,6 +99,12 @@ def sampler_name(config):
   return config["ldm_sampling"].get("sampler", "ddim")
 
 
+def noise_source_name(config):
+  """`ldm_sampling.noise_source`: "host" (default; the reference's YAML has no such key) or "device" (DESIGN.md
+  section 9)."""
+  return config["ldm_sampling"].get("noise_source", "host")
+
+
 def sampling_call(config, token_ids, seed):
   """(sampler method name, positional args, kwargs) of the call main() makes for `config`."""
   samp = config["ldm_sampling"]
@@ -156,6 +166,7 @@ def build_from_config(config, dtype=torch.bfloat16, device="cuda:0", seed=2, use
                                 with_encoder=with_encoder or None)
   return LatentDiffusionModelSampler(unet=unet, autoencoder=autoencoder, cond_stage_model=transformer,
                                      use_graph=use_graph, verbose=verbose, sampler=sampler_name(config),
+                                     noise_source=noise_source_name(config),
                                      **config["ldm"])
 
 
