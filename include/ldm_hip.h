@@ -72,7 +72,8 @@ int ldm_last_error(char* buf, int n);
  *   stride lda): m = (b, oy, ox) over [B][OH][OW], k = (kh, kw, ci) over 3x3xCin,
  *   source pixel (oy*stride + kh - 1, ox*stride + kw - 1), zero outside; with
  *   upsample = 1 the source image is first nearest-2x upsampled
- *   (src[i][j] = img[i/2][j/2]).  Cin must be a multiple of 128/sizeof(elem).
+ *   (src[i][j] = img[i/2][j/2]; 2H and 2W must then stay below 32768, H and W otherwise).
+ *   Cin must be a multiple of 128/sizeof(elem).
  *   Replaces: Conv2D 3x3 SAME (unet.py:22,40,71,375,378; autoencoder.py:32,35,
  *   148,275), pad(1,1)+stride-2 VALID (unet.py:26-27), ResizeNearestNeighbor+conv
  *   (unet.py:44-47, autoencoder.py:152-155).

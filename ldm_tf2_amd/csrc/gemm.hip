@@ -404,6 +404,10 @@ extern "C" int ldm_gemm(const ldm_gemm_params* p, void* stream) {
     LDM_CHECK_ARG(p->B > 0 && p->H > 0 && p->W > 0 && p->OH > 0 && p->OW > 0, "ldm_gemm(conv): dims");
     LDM_CHECK_ARG(p->H < 32768 && p->W < 32768, "ldm_gemm(conv): H/W too large");
     LDM_CHECK_ARG(!(p->upsample && p->stride != 1), "ldm_gemm(conv): upsample needs stride 1");
+    // the upsampled form packs the tap origin in the UPSAMPLED image into 16 bits each (a_aux of gemm_kernel.h /
+    // gemm3_kernel.h: (iy0 << 16) | (ix0 & 0xffff), ix0 read back as a short), so 2H and 2W must fit
+    LDM_CHECK_ARG(!p->upsample || (2 * p->H < 32768 && 2 * p->W < 32768),
+                  "ldm_gemm(conv): upsample needs 2*H and 2*W below 32768 (H=%d W=%d)", p->H, p->W);
     const int hs = p->upsample ? 2 * p->H : p->H, wsz = p->upsample ? 2 * p->W : p->W;
     LDM_CHECK_ARG(!p->no_lead_pad || p->stride == 2, "ldm_gemm(conv): no_lead_pad needs stride 2");
     const int padsum = p->no_lead_pad ? 1 : 2;
