@@ -481,6 +481,31 @@ int ldm_cfg_plms_update_rng(const float* eps_all, const float* xt, float* ring, 
                             const uint32_t* rng, int dec_index, float guidance_scale, int B, int64_t n_per_sample,
                             const float* z0, const float* mask, const float* q_coef, int channels, void* stream);
 
+/*
+ * Classifier-free guidance + table-weighted multistep update (sampler="deis"), float32:
+ * ldm_cfg_plms_update with the four Adams-Bashforth rows replaced by rows of a device table, so the weights can
+ * follow the step table actually walked.  With idx = *index, st = *start and j = clamp(st - idx, 0, 3):
+ *   w   = weights + idx * weights_pitch + 4 * j            (float32; entries 0 .. j are read, the others never)
+ *   e'  = w[0] e_i, then e' = fma(w[m], e_{i+m}, e') for m = 1 .. j          (this order, explicit fmas)
+ *   x0 = c1*xt - c2*e'; xt' = sqrt(a_prev)*x0 + sqrt(1 - a_prev)*e'; pred_x0_out (optional) receives x0.
+ * weights = [N_steps][4][4] floats with weights_pitch (>= 16) floats between the rows of consecutive indices; the
+ * kernel reads it through launch-uniform addresses.  Ring, start, blend, alignment and dec_index rules are those of
+ * ldm_cfg_plms_update: slots beyond j are not read, n_per_sample % 4 != 0 or a misaligned array is LDM_ERR_ARG.
+ */
+int ldm_cfg_ms_update(const float* eps_all, const float* xt, float* ring, float* xt_out, float* pred_x0_out,
+                      void* x_unet_out, int x_dtype, const float* coef, int32_t* index, const int32_t* start,
+                      const float* weights, int64_t weights_pitch, int dec_index, float guidance_scale, int B,
+                      int64_t n_per_sample, const float* z0, const float* mask, const float* q_noise,
+                      int64_t q_index_stride, const float* q_coef, int channels, void* stream);
+
+/* ldm_cfg_ms_update with the blend's Q[idx - 1] drawn from stream LDM_RNG_Q_STREAM + idx - 1, as
+ * ldm_cfg_plms_update_rng does; z0 = NULL: no blend, nothing is drawn. */
+int ldm_cfg_ms_update_rng(const float* eps_all, const float* xt, float* ring, float* xt_out, float* pred_x0_out,
+                          void* x_unet_out, int x_dtype, const float* coef, int32_t* index, const int32_t* start,
+                          const float* weights, int64_t weights_pitch, const uint32_t* rng, int dec_index,
+                          float guidance_scale, int B, int64_t n_per_sample, const float* z0, const float* mask,
+                          const float* q_coef, int channels, void* stream);
+
 /* decode_first_stage prologue (model_runners.py:426 + autoencoder.py:362,434):
  * out = Dense_{C->C}(latents / scale_factor), C <= 8; float32 in, out_dtype out. */
 int ldm_post_quant(const float* latents, float scale_factor, const float* kernel_io,

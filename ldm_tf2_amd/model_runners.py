@@ -25,6 +25,12 @@ four guided eps and the loop's start index on the device, the same captured grap
 noise_source="device"  draws every random number of the loops on the device: Philox4x32-10 keyed
 by the seed, counted by (element, global sample index, stream), formed in registers inside the step's update launch.
 No noise table is built or uploaded, and one captured graph serves any seed.
+
+step_spacing= / ddim_steps= choose the integer timesteps the loops walk: the reference's uniform
+table (default), N timesteps evenly spaced in lambda = half the log signal-to-noise ratio ("logsnr"), Karras et al.'s
+rho = 7 spacing in sigma ("karras"), or a table handed in.  Every derived table is built from the chosen one.
+sampler="deis" is the PLMS step with its weights computed for the table actually walked: a float32 device table
+[N][4][4] read by the one update launch.
 """
 from __future__ import annotations
 
@@ -72,6 +78,52 @@ Q_STREAM = (1 << 30) + 1         # + i: forward-diffusion noise Q[i] of DDIM ind
 XT_STREAM = 0                    # x_T
 ETA_STREAM = 1 << 29             # + i: eta noise of the step at DDIM index i
 NOISE_SOURCES = ("host", "device")
+STEP_SPACINGS = ("uniform", "logsnr", "karras")
+KARRAS_RHO = 7.
+
+
+def log_snr_half(alphas_cumprod):
+  """lambda(t) = 0.5 * ln(abar[t] / (1 - abar[t])), float64: it falls as t rises."""
+  ac = np.asarray(alphas_cumprod, dtype=np.float64)
+  return 0.5 * np.log(ac / (1. - ac))
+
+
+def spaced_steps(alphas_cumprod, num_ddim_steps, top, spacing):
+  """The "logsnr" / "karras" step table: num_ddim_steps targets evenly spaced in lambda, or in
+  sigma^(1/rho) with sigma = sqrt((1 - abar) / abar), between timestep 0 (exclusive) and `top` (inclusive); each
+  target becomes the integer timestep with the nearest lambda, at least 1 and above its predecessor; the last one
+  is `top`.  int32, ascending."""
+  ac = np.asarray(alphas_cumprod, dtype=np.float64)
+  lam = log_snr_half(ac)
+  n = int(num_ddim_steps)
+  if spacing == "logsnr":
+    targets = np.linspace(lam[0], lam[top], n + 1)[1:]
+  elif spacing == "karras":
+    sigma = np.sqrt((1. - ac) / ac)
+    targets = -np.log(np.linspace(sigma[0] ** (1. / KARRAS_RHO), sigma[top] ** (1. / KARRAS_RHO), n + 1)[1:]
+                      ** KARRAS_RHO)
+  else:
+    raise ValueError(f"step_spacing must be one of {STEP_SPACINGS}, got {spacing!r}")
+  steps = np.empty(n, dtype=np.int32)
+  for j, target in enumerate(targets):
+    t = max(int(np.argmin(np.abs(lam - target))), 1)
+    steps[j] = t if j == 0 else max(t, steps[j - 1] + 1)
+  steps[-1] = top
+  return steps
+
+
+def check_steps(steps, num_steps, num_ddim_steps):
+  """A step table as int32: strictly ascending timesteps in [1, num_steps - 1], num_ddim_steps of them."""
+  arr = np.asarray(steps)
+  if arr.ndim != 1 or arr.size == 0 or not np.issubdtype(arr.dtype, np.integer):
+    raise ValueError(f"ddim_steps must be a non-empty 1-D sequence of ints, got {steps!r}")
+  if arr.size != num_ddim_steps:
+    raise ValueError(f"ddim_steps has {arr.size} entries, num_ddim_steps is {num_ddim_steps}")
+  if arr.min() < 1 or arr.max() > num_steps - 1:
+    raise ValueError(f"ddim_steps must lie in [1, {num_steps - 1}], got [{int(arr.min())}, {int(arr.max())}]")
+  if np.any(np.diff(arr.astype(np.int64)) <= 0):
+    raise ValueError("ddim_steps must be strictly ascending")
+  return arr.astype(np.int32)
 
 
 def img2img_start(strength, num_ddim_steps):
@@ -102,7 +154,12 @@ def latent_mask(pixel_mask, f):
 class LatentDiffusionModel(object):
 
   def __init__(self, unet, autoencoder, cond_stage_model, num_steps=1000, beta_start=1e-4,
-               beta_end=2e-2, v_posterior=0., scale_factor=0.18215, eta=0., num_ddim_steps=50):
+               beta_end=2e-2, v_posterior=0., scale_factor=0.18215, eta=0., num_ddim_steps=50, step_spacing="uniform",
+               ddim_steps=None):
+    if step_spacing not in STEP_SPACINGS:
+      raise ValueError(f"step_spacing must be one of {STEP_SPACINGS}, got {step_spacing!r}")
+    if ddim_steps is not None and step_spacing != "uniform":
+      raise ValueError(f"ddim_steps is a step table of its own: step_spacing={step_spacing!r} cannot be given with it")
     self._unet = unet
     self._autoencoder = autoencoder
     self._cond_stage_model = cond_stage_model
@@ -113,6 +170,7 @@ class LatentDiffusionModel(object):
     self._scale_factor = scale_factor
     self._eta = eta
     self._num_ddim_steps = num_ddim_steps
+    self._step_spacing = step_spacing if ddim_steps is None else "custom"
 
     # model_runners.py:379-384 (linspace and square in float32, then float64)
     ls = _tf_linspace_f32(beta_start ** 0.5, beta_end ** 0.5, num_steps)
@@ -121,14 +179,23 @@ class LatentDiffusionModel(object):
     self._alphas_cumprod = np.cumprod(self._alphas, axis=0)
     self._sqrt_recip_alphas_cumprod = np.sqrt(1. / self._alphas_cumprod)
     self._sqrt_recipm1_alphas_cumprod = np.sqrt(1. / self._alphas_cumprod - 1)
-    # :406-409
-    self._ddim_steps = np.arange(0, num_steps, num_steps // num_ddim_steps, dtype=np.int32)
-    if self._num_ddim_steps < self._num_steps:
-      self._ddim_steps = self._ddim_steps + 1
-    if self._ddim_steps.max() >= num_steps:
-      # tf.gather on CPU raises for an out-of-range index; N must divide num_steps
-      raise IndexError(f"ddim step {int(self._ddim_steps.max())} out of range: num_ddim_steps="
-                       f"{num_ddim_steps} must divide num_steps={num_steps}")
+    if ddim_steps is not None:
+      # a table handed in (the N-divides-num_steps rule belongs to the uniform table)
+      self._ddim_steps = check_steps(ddim_steps, num_steps, num_ddim_steps)
+    else:
+      # :406-409
+      self._ddim_steps = np.arange(0, num_steps, num_steps // num_ddim_steps, dtype=np.int32)
+      if self._num_ddim_steps < self._num_steps:
+        self._ddim_steps = self._ddim_steps + 1
+      if self._ddim_steps.max() >= num_steps:
+        # tf.gather on CPU raises for an out-of-range index; N must divide num_steps
+        raise IndexError(f"ddim step {int(self._ddim_steps.max())} out of range: num_ddim_steps="
+                         f"{num_ddim_steps} must divide num_steps={num_steps}")
+      if step_spacing != "uniform":
+        # another table on the same interval (the uniform table's last entry stays the last)
+        self._ddim_steps = check_steps(
+            spaced_steps(self._alphas_cumprod, num_ddim_steps, int(self._ddim_steps[-1]), step_spacing), num_steps,
+            num_ddim_steps)
     alphas_cumprod = self._alphas_cumprod[self._ddim_steps]
     # :412-415 -- a_prev at index 0 is abar[0], not 1
     self._ddim_alphas_cumprod_prev = np.concatenate(
@@ -149,6 +216,27 @@ class LatentDiffusionModel(object):
     self._q_tables = None
     self._noise_source = "host"
     self._rng = None
+    self._ms_weights = None
+
+  def multistep_weights(self):
+    """float64 [N][4][4]: row [i][j] = the weights of (e_i, .., e_{i+j}) at DDIM index i with j
+    earlier steps in the loop (j + 1 entries, the rest zero; rows whose history would lie beyond index N - 1 stay
+    zero and are never read)."""
+    lam = log_snr_half(self._alphas_cumprod[self._ddim_steps])
+    lam_prev = log_snr_half(self._ddim_alphas_cumprod_prev)
+    n = len(self._ddim_steps)
+    w = np.zeros((n, 4, 4), dtype=np.float64)
+    for i in range(n):
+      for j in range(min(3, n - 1 - i) + 1):
+        w[i, j, :j + 1] = deis_weights(lam[i:i + j + 1], lam_prev[i])
+    return w
+
+  def _device_ms_weights(self):
+    """The float32 cast of multistep_weights() on the device, made on first use; the sampler owns it (a captured
+    graph reads it at a fixed address)."""
+    if self._ms_weights is None:
+      self._ms_weights = torch.from_numpy(self.multistep_weights().astype(np.float32)).to(self.device).contiguous()
+    return self._ms_weights
 
   def _set_rng(self, seed, first_sample_index):
     """The device generator's state uint32[4] = {seed_lo, seed_hi, first_sample_index, 0} (seed mod 2^64; int32
@@ -256,7 +344,34 @@ PLMS_WEIGHTS = (
     (23. / 12., -16. / 12., 5. / 12.),
     (55. / 24., -59. / 24., 37. / 24., -9. / 24.),
 )
-SAMPLERS = ("ddim", "plms")
+SAMPLERS = ("ddim", "plms", "deis")
+MULTISTEP = ("plms", "deis")     # samplers with a ring of guided eps and a loop start index; deterministic
+_GL_X, _GL_W = np.polynomial.legendre.leggauss(16)
+
+
+def deis_weights(lams, lam_target):
+  """DEIS (Zhang & Chen 2022), the exponential-integrator Adams-Bashforth weights in lambda: nodes lams = (l_0, .., l_j)
+  (this step's lambda, then the j earlier steps'), the step lands on lam_target > l_0.
+    w[m] = int_{l_0}^{l'} e^{-l} L_m(l) dl / int_{l_0}^{l'} e^{-l} dl,  L_m = the Lagrange basis on the nodes.
+  With l = l_0 + h s both integrals run over s in [0, 1] with the weight e^{-h s}: 16-point Gauss-Legendre in float64
+  (the integrand is e^{-h s} times a polynomial of degree <= 3 and h is a few units at most; the closed form in
+  tests/deis_ref.py agrees to 1e-12).  Sum_m w[m] = 1; j = 0 gives (1,), the DDIM step."""
+  lams = np.asarray(lams, dtype=np.float64)
+  h = float(lam_target) - lams[0]
+  if not h > 0.:
+    raise ValueError(f"the step must raise lambda: {lams[0]} -> {lam_target}")
+  nodes = (lams - lams[0]) / h
+  s = 0.5 * (_GL_X + 1.)
+  ex = _GL_W * np.exp(-h * s)
+  den = ex.sum()
+  w = np.empty(len(nodes), dtype=np.float64)
+  for m in range(len(nodes)):
+    basis = np.ones_like(s)
+    for k in range(len(nodes)):
+      if k != m:
+        basis = basis * ((s - nodes[k]) / (nodes[m] - nodes[k]))
+    w[m] = (ex * basis).sum() / den
+  return w
 
 
 class LatentDiffusionModelSampler(LatentDiffusionModel):
@@ -269,8 +384,8 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     if noise_source not in NOISE_SOURCES:
       raise ValueError(f"noise_source must be one of {NOISE_SOURCES}, got {noise_source!r}")
     self._noise_source = noise_source
-    if sampler == "plms" and self._eta != 0:
-      raise ValueError(f"sampler='plms' is deterministic: eta must be 0, got {self._eta}")
+    if sampler in MULTISTEP and self._eta != 0:
+      raise ValueError(f"sampler={sampler!r} is deterministic: eta must be 0, got {self._eta}")
     self._sampler = sampler
     self._use_graph = use_graph
     self._use_temb_table = bool(temb_table)      # A/B: False = four temb launches + a decrement launch per step
@@ -306,19 +421,21 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       self._xt = torch.empty(B, h, w, c, dtype=f32, device=dev)
       self._x2 = torch.empty(2 * B, h, w, c, dtype=f32, device=dev)
       self._eps = torch.empty(2 * B, h, w, c, dtype=f32, device=dev)
-      if self._sampler == "plms":
+      if self._sampler in MULTISTEP:
         # the last four guided eps by DDIM index & 3 (never initialised: a step reads only slots its own loop wrote)
         # and the DDIM index of the loop's first step
         self._ring = torch.empty(4, B, h, w, c, dtype=f32, device=dev)
         self._start = torch.zeros(1, dtype=torch.int32, device=dev)
+      if self._sampler == "deis":
+        self._device_ms_weights()                # (made before any capture: the graph reads it at a fixed address)
       if self._noise_source == "device" and self._rng is None:
         self._rng = torch.zeros(4, dtype=torch.int32, device=dev)    # (written by each loop's reset)
       self._state_key = key
       self._graph = None
 
   def _set_loop_start(self, start_index):
-    """PLMS: the loop's first step is the one at DDIM index `start_index` (it has no history)."""
-    if self._sampler == "plms":
+    """PLMS / DEIS: the loop's first step is the one at DDIM index `start_index` (it has no history)."""
+    if self._sampler in MULTISTEP:
       self._start.fill_(int(start_index))
 
   def _owned(self, name, src, shape, dtype=torch.float32):
@@ -354,7 +471,12 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       if masked:
         blend = dict(z0=self._z0_buf, mask=self._mask_buf, q_coef=self._device_q_tables()[2])
       dec = dec_index and not self._pre_dec
-      if self._sampler == "plms":
+      if self._sampler == "deis":
+        assert not clip_denoised
+        ops.cfg_ms_update_rng(self._eps, self._xt, self._xt, self._ring, self._coef_dev, self._index_dev,
+                              self._start, self._device_ms_weights(), self._rng, guidance_scale, x_unet_out=self._x2,
+                              dec_index=dec, pred_x0_out=pred_x0_out, **blend)
+      elif self._sampler == "plms":
         assert not clip_denoised
         ops.cfg_plms_update_rng(self._eps, self._xt, self._xt, self._ring, self._coef_dev, self._index_dev,
                                 self._start, self._rng, guidance_scale, x_unet_out=self._x2, dec_index=dec,
@@ -364,13 +486,18 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
                                 guidance_scale, x_unet_out=self._x2, dec_index=dec, clip_denoised=clip_denoised,
                                 pred_x0_out=pred_x0_out, **blend)
       return
-    if self._sampler == "plms":
+    if self._sampler in MULTISTEP:
       # (eta = 0: no noise table; the loops never clip)
       assert noise_table is None and not clip_denoised
       blend = {}
       if masked:
         blend = dict(z0=self._z0_buf, mask=self._mask_buf, q_noise=self._q_buf, q_coef=self._device_q_tables()[2],
                      q_index_stride=self._q_buf[0].numel())
+      if self._sampler == "deis":
+        ops.cfg_ms_update(self._eps, self._xt, self._xt, self._ring, self._coef_dev, self._index_dev, self._start,
+                          self._device_ms_weights(), guidance_scale, x_unet_out=self._x2,
+                          dec_index=dec_index and not self._pre_dec, pred_x0_out=pred_x0_out, **blend)
+        return
       ops.cfg_plms_update(self._eps, self._xt, self._xt, self._ring, self._coef_dev, self._index_dev, self._start,
                           guidance_scale, x_unet_out=self._x2, dec_index=dec_index and not self._pre_dec,
                           pred_x0_out=pred_x0_out, **blend)
@@ -392,7 +519,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
                   return_pred_x0=False, noise=None):
     """model_runners.py:438-472 for a host-side `index`.  `noise` [B,h,w,c] replaces
     the reference's tf.random.normal draw (zeros when omitted; irrelevant at eta=0).
-    Always the DDIM step, also on a sampler="plms" sampler: a single step has no history."""
+    Always the DDIM step, also on a sampler="plms" or "deis" sampler: a single step has no history."""
     xt = torch.as_tensor(xt, dtype=torch.float32).to(self.device).contiguous()
     B, h, w, c = xt.shape
     self._alloc_state(B, h, w, c)
@@ -517,7 +644,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       self._set_loop_start(n - 1)
 
     gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, False, self._noise_source, rng,
-            self._sampler)
+            self._step_spacing, self._sampler)
     self._sample_loop(n, reset, lambda dec: self._step(guidance_scale, False, noise_table, dec_index=dec, rng=rng),
                       gkey, record)
     return self._finish(self._xt)
@@ -619,7 +746,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       self._set_loop_start(k - 1)
 
     gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, masked, self._noise_source, rng,
-            self._sampler)
+            self._step_spacing, self._sampler)
     self._sample_loop(k, reset, lambda dec: self._step(guidance_scale, False, noise_table, dec_index=dec,
                                                         masked=masked, rng=rng), gkey, record)
     return self._finish(self._xt)

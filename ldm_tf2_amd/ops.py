@@ -20,7 +20,8 @@ __all__ = [
     "ACT_NONE", "ACT_GELU", "ACT_GEGLU", "ACT_SILU", "F32", "BF16", "code", "linear", "conv3x3",
     "bmm_nt", "conv3x3_small", "groupnorm", "layernorm", "softmax_rows", "attention",
     "time_embedding", "gemv", "cfg_ddim_update", "cfg_ddim_update_masked", "cfg_plms_update", "q_sample",
-    "philox_u32", "normal_fill", "q_sample_rng", "cfg_ddim_update_rng", "cfg_plms_update_rng", "post_quant", "vq_nearest", "embedding",
+    "philox_u32", "normal_fill", "q_sample_rng", "cfg_ddim_update_rng", "cfg_plms_update_rng", "cfg_ms_update",
+    "cfg_ms_update_rng", "post_quant", "vq_nearest", "embedding",
     "minmax_u8", "cast",
 ]
 
@@ -953,6 +954,56 @@ def cfg_plms_update_rng(eps_all, xt, xt_out, ring, coef, index, start, rng, guid
       _ptr(_f32(pred_x0_out, "pred_x0_out")), _ptr(x_unet_out), xd, _ptr(_f32(coef, "coef")), _ptr(index),
       _ptr(start), _rng(rng), int(bool(dec_index)), float(guidance_scale), B, n, _ptr(_f32(z0, "z0")),
       _ptr(_f32(mask, "mask")), _ptr(_f32(q_coef, "q_coef")), xt.shape[-1], _stream()), "ldm_cfg_plms_update_rng")
+  return xt_out
+
+
+def _ms_weights(weights, coef):
+  """The weight table of ldm_cfg_ms_update: float32 [N,4,4] (N = rows of coef), rows of 16 floats `pitch` apart."""
+  assert weights.dim() == 3 and tuple(weights.shape[1:]) == (4, 4) and weights.shape[0] == coef.shape[0]
+  assert weights.stride(2) == 1 and weights.stride(1) == 4 and weights.stride(0) >= 16
+  return _ptr(_f32(weights, "weights")), weights.stride(0)
+
+
+def cfg_ms_update(eps_all, xt, xt_out, ring, coef, index, start, weights, guidance_scale, x_unet_out=None,
+                  dec_index=False, pred_x0_out=None, z0=None, mask=None, q_noise=None, q_coef=None, q_index_stride=0):
+  """CFG + table-weighted multistep update (include/ldm_hip.h): cfg_plms_update with the weights of the step at
+  *index with j = min(*start - *index, 3) earlier steps read from weights[*index, j, :j + 1] (float32 [N,4,4] on the
+  device) instead of the Adams-Bashforth constants.  Ring, start and the blend as cfg_plms_update."""
+  B = xt.shape[0]
+  n = xt.numel() // B
+  c = xt.shape[-1]
+  assert ring.is_contiguous() and ring.numel() == 4 * xt.numel()
+  assert index.dtype == torch.int32 and start.dtype == torch.int32
+  if z0 is not None:
+    assert z0.is_contiguous() and z0.numel() == xt.numel()
+    assert mask.is_contiguous() and mask.numel() * c == xt.numel()
+    assert q_noise.is_contiguous() and q_coef.is_contiguous() and q_coef.shape == (coef.shape[0], 2)
+    assert q_noise.numel() >= (q_coef.shape[0] - 1) * q_index_stride + xt.numel()
+  xd = code(x_unet_out.dtype) if x_unet_out is not None else F32
+  check(lib.ldm_cfg_ms_update(
+      _ptr(_f32(eps_all, "eps_all")), _ptr(_f32(xt, "xt")), _ptr(_f32(ring, "ring")), _ptr(_f32(xt_out, "xt_out")),
+      _ptr(_f32(pred_x0_out, "pred_x0_out")), _ptr(x_unet_out), xd, _ptr(_f32(coef, "coef")), _ptr(index),
+      _ptr(start), *_ms_weights(weights, coef), int(bool(dec_index)), float(guidance_scale), B, n,
+      _ptr(_f32(z0, "z0")), _ptr(_f32(mask, "mask")), _ptr(_f32(q_noise, "q_noise")), int(q_index_stride),
+      _ptr(_f32(q_coef, "q_coef")), c, _stream()), "ldm_cfg_ms_update")
+  return xt_out
+
+
+def cfg_ms_update_rng(eps_all, xt, xt_out, ring, coef, index, start, weights, rng, guidance_scale, x_unet_out=None,
+                      dec_index=False, pred_x0_out=None, z0=None, mask=None, q_coef=None):
+  """cfg_ms_update with the blend's Q drawn in the launch from `rng` (stream Q_STREAM + *index - 1)."""
+  B = xt.shape[0]
+  n = xt.numel() // B
+  assert ring.is_contiguous() and ring.numel() == 4 * xt.numel()
+  assert index.dtype == torch.int32 and start.dtype == torch.int32
+  _blend_rng(xt, coef, z0, mask, q_coef)
+  xd = code(x_unet_out.dtype) if x_unet_out is not None else F32
+  check(lib.ldm_cfg_ms_update_rng(
+      _ptr(_f32(eps_all, "eps_all")), _ptr(_f32(xt, "xt")), _ptr(_f32(ring, "ring")), _ptr(_f32(xt_out, "xt_out")),
+      _ptr(_f32(pred_x0_out, "pred_x0_out")), _ptr(x_unet_out), xd, _ptr(_f32(coef, "coef")), _ptr(index),
+      _ptr(start), *_ms_weights(weights, coef), _rng(rng), int(bool(dec_index)), float(guidance_scale), B, n,
+      _ptr(_f32(z0, "z0")), _ptr(_f32(mask, "mask")), _ptr(_f32(q_coef, "q_coef")), xt.shape[-1], _stream()),
+        "ldm_cfg_ms_update_rng")
   return xt_out
 
 

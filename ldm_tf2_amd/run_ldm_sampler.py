@@ -22,8 +22,12 @@ img2img / inpainting: optional `ldm_sampling` keys `init_image` (a .npy of uint8
 [B,H,W], nonzero = keep; needs `init_image`).  With `init_image` the autoencoder is built
 or loaded with its encoder.  Without these keys nothing changes.
 
-Solver: optional `ldm_sampling` key `sampler`, `ddim` (default) or `plms` (pseudo linear multistep, needs
-`ldm.eta` 0; DESIGN.md section 8); every loop above honours it.
+Solver: optional `ldm_sampling` key `sampler`, `ddim` (default), `plms` (pseudo linear multistep, needs
+`ldm.eta` 0) or `deis` (the same step with weights computed for the step table walked, needs
+`ldm.eta` 0; DESIGN.md section 10); every loop above honours it.
+
+Step table: optional `ldm_sampling` key `step_spacing`, `uniform` (default: the reference's table), `logsnr` or
+`karras`; every loop and every solver runs on any of them.
 
 Noise: optional `ldm_sampling` key `noise_source`, `host` (default: NumPy generators, tables uploaded before the loop)
 or `device` (Philox streams drawn inside the update launches, no tables).  The two sources draw
@@ -99,6 +103,12 @@ def sampler_name(config):
   return config["ldm_sampling"].get("sampler", "ddim")
 
 
+def step_spacing_name(config):
+  """`ldm_sampling.step_spacing`: "uniform" (default; the reference's YAML has no such key), "logsnr" or "karras"
+  (DESIGN.md section 10)."""
+  return config["ldm_sampling"].get("step_spacing", "uniform")
+
+
 def noise_source_name(config):
   """`ldm_sampling.noise_source`: "host" (default; the reference's YAML has no such key) or "device" (DESIGN.md
   section 9)."""
@@ -167,6 +177,7 @@ def build_from_config(config, dtype=torch.bfloat16, device="cuda:0", seed=2, use
   return LatentDiffusionModelSampler(unet=unet, autoencoder=autoencoder, cond_stage_model=transformer,
                                      use_graph=use_graph, verbose=verbose, sampler=sampler_name(config),
                                      noise_source=noise_source_name(config),
+                                     step_spacing=step_spacing_name(config),
                                      **config["ldm"])
 
 
