@@ -506,6 +506,28 @@ int ldm_cfg_ms_update_rng(const float* eps_all, const float* xt, float* ring, fl
                           float guidance_scale, int B, int64_t n_per_sample, const float* z0, const float* mask,
                           const float* q_coef, int channels, void* stream);
 
+/*
+ * Guidance schedule, float32: ldm_cfg_ms_update with the guidance scale read from a device
+ * table and a conditional-only form.  With idx = *index:
+ *   guided != 0:  e_i = eps_u + gtab[idx] * (eps_c - eps_u)      (gtab float32 [N_steps], a launch-uniform address:
+ *                                                                 one captured launch serves every schedule)
+ *   guided == 0:  e_i = eps_c, the second half of eps_all [2B][n]; the first half is NOT read (the conditional-only
+ *                 U-Net evaluation leaves it unwritten) and gtab[idx] is not read either.
+ * weights != NULL: e_i enters the ring and e' is the weighted sum of ldm_cfg_ms_update (ring, start, weights and
+ * weights_pitch as there; the PLMS constants as a table give PLMS).  weights == NULL: e' = e_i, the DDIM step at
+ * sigma = 0; ring and start may be NULL and are not touched.  x0 = c1*xt - c2*e'; xt' = sqrt(a_prev)*x0 +
+ * sqrt(1 - a_prev)*e'.  x_unet_out (optional) always receives both halves concat([xt', xt']), whichever form ran, so
+ * the next step may take either.  rng != NULL: the blend's Q[idx - 1] is drawn from stream LDM_RNG_Q_STREAM + idx - 1
+ * (q_noise is ignored); rng == NULL: read from q_noise.  z0 = NULL: no blend.  Alignment, n_per_sample % 4 and
+ * dec_index rules are those of ldm_cfg_ms_update.
+ */
+int ldm_cfg_sched_update(const float* eps_all, const float* xt, float* ring, float* xt_out, float* pred_x0_out,
+                         void* x_unet_out, int x_dtype, const float* coef, const float* gtab, int32_t* index,
+                         const int32_t* start, const float* weights, int64_t weights_pitch, const uint32_t* rng,
+                         int guided, int dec_index, int B, int64_t n_per_sample, const float* z0, const float* mask,
+                         const float* q_noise, int64_t q_index_stride, const float* q_coef, int channels,
+                         void* stream);
+
 /* decode_first_stage prologue (model_runners.py:426 + autoencoder.py:362,434):
  * out = Dense_{C->C}(latents / scale_factor), C <= 8; float32 in, out_dtype out. */
 int ldm_post_quant(const float* latents, float scale_factor, const float* kernel_io,

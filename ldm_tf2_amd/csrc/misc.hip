@@ -669,6 +669,106 @@ __global__ __launch_bounds__(256) void cfg_ms_kernel(const float* __restrict__ e
   }
 }
 
+// ---- guidance schedule: CFG by a device table / conditional-only steps -----------------
+// cfg_ms_kernel with the scale read from a device table, gs = gtab[idx] (a launch-uniform address, like coef: one
+// captured launch serves every schedule), and a second form of the same body.  Guided: e0 = eu + gs * (ec - eu), the
+// expression of the kernels above.  !Guided: e0 = ec, the conditional half of eps_all [2B][n]; the unconditional
+// half is never loaded (the conditional-only U-Net evaluation does not write it: it may hold NaN).  weights == NULL:
+// no history (j = 0, e' = e0: the DDIM step at sigma = 0), ring and start are not touched.  Both halves of x_unet
+// are always written, so the next step may take either form.  Rng and the blend as in cfg_ms_kernel.
+template <typename TX, bool Guided, bool Rng>
+__global__ __launch_bounds__(256) void cfg_sched_kernel(const float* __restrict__ eps_all, const float* xt,
+                                                        float* __restrict__ ring, float* xt_out,
+                                                        float* __restrict__ pred_x0_out, TX* __restrict__ x_unet,
+                                                        const float* coef, const float* __restrict__ gtab,
+                                                        const int32_t* index, const int32_t* start,
+                                                        const float* __restrict__ weights, int64_t w_pitch,
+                                                        const uint32_t* __restrict__ rng, uint32_t q_stream, int B,
+                                                        int64_t n, BlendArgs bl) {
+  const int idx = *index;
+  int j = 0;
+  float w0 = 1.f, w1 = 0.f, w2 = 0.f, w3 = 0.f;
+  if (weights) {
+    const int d = *start - idx;
+    j = d < 0 ? 0 : (d > 3 ? 3 : d);
+    const float* wr = weights + (int64_t)idx * w_pitch + 4 * j;
+    w0 = wr[0];
+    w1 = j >= 1 ? wr[1] : 0.f;
+    w2 = j >= 2 ? wr[2] : 0.f;
+    w3 = j >= 3 ? wr[3] : 0.f;
+  }
+  float gs = 1.f;
+  if constexpr (Guided) gs = gtab[idx];
+  const float c1 = coef[idx * 4 + 0], c2 = coef[idx * 4 + 1], a_prev = coef[idx * 4 + 2];
+  const float sa = sqrtf(a_prev);
+  const float sb = sqrtf(1.0f - a_prev);
+  const int64_t total = (int64_t)B * n;
+  float* e_out = weights ? ring + (int64_t)(idx & 3) * total : nullptr;
+  const float *e1 = nullptr, *e2 = nullptr, *e3 = nullptr;
+  if (weights) {
+    e1 = ring + (int64_t)((idx + 1) & 3) * total;
+    e2 = ring + (int64_t)((idx + 2) & 3) * total;
+    e3 = ring + (int64_t)((idx + 3) & 3) * total;
+  }
+  const bool blend = bl.z0 != nullptr && idx >= 1;   // never reads or draws a row at -1
+  float qa = 0.f, qb = 0.f;
+  const float* qn = nullptr;
+  if (blend) {
+    qa = bl.q_coef[(idx - 1) * 2 + 0];
+    qb = bl.q_coef[(idx - 1) * 2 + 1];
+    if constexpr (!Rng) qn = bl.q_noise + (int64_t)(idx - 1) * bl.q_stride;
+  }
+  for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < total; i += (int64_t)gridDim.x * 256 * 4) {
+    const f32x4 ec = *(const f32x4*)(eps_all + total + i);
+    const f32x4 x = *(const f32x4*)(xt + i);
+    f32x4 e0 = ec;
+    if constexpr (Guided) {
+      const f32x4 eu = *(const f32x4*)(eps_all + i);
+      e0 = eu + gs * (ec - eu);
+    }
+    f32x4 ep;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ep[k] = w0 * e0[k];
+    if (j >= 1) {
+      const f32x4 h = *(const f32x4*)(e1 + i);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) ep[k] = __builtin_fmaf(w1, h[k], ep[k]);
+    }
+    if (j >= 2) {
+      const f32x4 h = *(const f32x4*)(e2 + i);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) ep[k] = __builtin_fmaf(w2, h[k], ep[k]);
+    }
+    if (j >= 3) {
+      const f32x4 h = *(const f32x4*)(e3 + i);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) ep[k] = __builtin_fmaf(w3, h[k], ep[k]);
+    }
+    const f32x4 x0 = c1 * x - c2 * ep;
+    f32x4 o = sa * x0 + sb * ep;
+    if (blend) {
+      const f32x4 z = *(const f32x4*)(bl.z0 + i);
+      f32x4 qe;
+      if constexpr (Rng) {
+        const int64_t b = i / n;
+        qe = rng_normal4(rng, (uint32_t)((i - b * n) >> 2), (uint32_t)b, q_stream + (uint32_t)(idx - 1));
+      } else {
+        qe = *(const f32x4*)(qn + i);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float m = bl.mask[(i + k) / bl.channels];
+        const float q = q_sample_f(qa, qb, z[k], qe[k]);
+        o[k] = m * q + (1.f - m) * o[k];
+      }
+    }
+    if (e_out) *(f32x4*)(e_out + i) = e0;
+    *(f32x4*)(xt_out + i) = o;
+    if (pred_x0_out) *(f32x4*)(pred_x0_out + i) = x0;
+    if (x_unet) { st4(x_unet + i, o); st4(x_unet + total + i, o); }
+  }
+}
+
 // ---- out[:] = table[i][:], i = *index (pre_decrement: i = --*index first) --------------------------
 // ONE workgroup: the thread that moves the loop counter is in the same workgroup as every reader of it, so the
 // decrement needs no launch of its own, and every later launch of the step sees the new value.
@@ -1229,6 +1329,54 @@ extern "C" int ldm_cfg_ms_update_rng(const float* eps_all, const float* xt, floa
   return cfg_ms_launch("ldm_cfg_ms_update_rng", true, eps_all, xt, ring, xt_out, pred_x0_out, x_unet_out, x_dtype,
                        coef, index, start, weights, weights_pitch, rng, dec_index, guidance_scale, B, n_per_sample, z0,
                        mask, nullptr, 0, q_coef, channels, stream);
+}
+extern "C" int ldm_cfg_sched_update(const float* eps_all, const float* xt, float* ring, float* xt_out,
+                                    float* pred_x0_out, void* x_unet_out, int x_dtype, const float* coef,
+                                    const float* gtab, int32_t* index, const int32_t* start, const float* weights,
+                                    int64_t weights_pitch, const uint32_t* rng, int guided, int dec_index, int B,
+                                    int64_t n_per_sample, const float* z0, const float* mask, const float* q_noise,
+                                    int64_t q_index_stride, const float* q_coef, int channels, void* stream) {
+  const char* what = "ldm_cfg_sched_update";
+  const bool draws = rng != nullptr;
+  LDM_CHECK_ARG(eps_all && xt && xt_out && coef && gtab && index, "%s: null pointer", what);
+  LDM_CHECK_ARG(!weights || (ring && start), "%s: weights without ring / start", what);
+  LDM_CHECK_ARG(DT_OK(x_dtype) && B > 0 && n_per_sample > 0 && n_per_sample % 4 == 0,
+                "%s: bad args (n_per_sample=%lld must be a positive multiple of 4)", what, (long long)n_per_sample);
+  LDM_CHECK_ARG(!weights || weights_pitch >= 16, "%s: weights_pitch=%lld, a row holds 4 x 4 floats", what,
+                (long long)weights_pitch);
+  LDM_CHECK_ARG(AL16(eps_all) && AL16(xt) && AL16(ring) && AL16(xt_out) && AL16(pred_x0_out) && AL16(z0) &&
+                    XU_OK(x_unet_out, x_dtype) && (draws || !z0 || (AL16(q_noise) && q_index_stride % 4 == 0)),
+                "%s: arrays must be 16-byte aligned (q_index_stride a multiple of 4)", what);
+  BlendArgs bl{};
+  if (z0) {
+    LDM_CHECK_ARG(mask && q_coef && (draws || q_noise), "%s: z0 without mask / q_noise / q_coef", what);
+    LDM_CHECK_ARG(channels > 0 && n_per_sample % channels == 0 && q_index_stride >= 0,
+                  "%s: bad args (n_per_sample=%lld, channels=%d)", what, (long long)n_per_sample, channels);
+    bl = BlendArgs{z0, mask, draws ? nullptr : q_noise, draws ? 0 : q_index_stride, q_coef, channels};
+  }
+  if (!weights) ring = nullptr;                      // (no history: the ring is neither read nor written)
+  hipStream_t s = (hipStream_t)stream;
+  dim3 g(grid_for((int64_t)B * n_per_sample / 4, 256, 1024));
+#define LAUNCH_SCHED(TX, GUIDED, RNG)                                                                              \
+  hipLaunchKernelGGL((cfg_sched_kernel<TX, GUIDED, RNG>), g, dim3(256), 0, s, eps_all, xt, ring, xt_out,           \
+                     pred_x0_out, (TX*)x_unet_out, coef, gtab, index, start, weights, weights_pitch, rng,           \
+                     (uint32_t)LDM_RNG_Q_STREAM, B, n_per_sample, bl)
+#define LAUNCH_SCHED_TX(GUIDED, RNG) \
+  do { if (x_dtype == LDM_BF16) LAUNCH_SCHED(bf16_t, GUIDED, RNG); else LAUNCH_SCHED(float, GUIDED, RNG); } while (0)
+  if (guided) {
+    if (draws) LAUNCH_SCHED_TX(true, true); else LAUNCH_SCHED_TX(true, false);
+  } else {
+    if (draws) LAUNCH_SCHED_TX(false, true); else LAUNCH_SCHED_TX(false, false);
+  }
+#undef LAUNCH_SCHED_TX
+#undef LAUNCH_SCHED
+  int st = ldm_launch_status(what);
+  if (st != LDM_OK) return st;
+  if (dec_index) {
+    hipLaunchKernelGGL(dec_index_kernel, dim3(1), dim3(1), 0, s, index);
+    st = ldm_launch_status(what);
+  }
+  return st;
 }
 #undef AL16
 #undef XU_OK

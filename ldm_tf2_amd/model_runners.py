@@ -31,6 +31,12 @@ table (default), N timesteps evenly spaced in lambda = half the log signal-to-no
 rho = 7 spacing in sigma ("karras"), or a table handed in.  Every derived table is built from the chosen one.
 sampler="deis" is the PLMS step with its weights computed for the table actually walked: a float32 device table
 [N][4][4] read by the one update launch.
+
+guidance_scale=[g_0 .. g_{N-1}] / guidance_interval=(t_lo, t_hi) give every DDIM index its own
+guidance scale: a float32 device table read by the one update launch (ldm_cfg_sched_update), so no scale is frozen
+into a captured graph.  A step whose scale is exactly 1 is unguided: its eps is the conditional one by definition,
+and the U-Net runs on the conditional rows alone against the resident context.  A loop replays one of two captured
+graphs per step.  eta must be 0 there; a float scale without an interval takes the path above unchanged.
 """
 from __future__ import annotations
 
@@ -149,6 +155,35 @@ def latent_mask(pixel_mask, f):
   B, H, W = m.shape
   keep = (m != 0).reshape(B, H // f, f, W // f, f).all(axis=(2, 4))
   return keep.astype(np.float32)
+
+
+def guidance_table(steps, guidance_scale, guidance_interval=None):
+  """The per-step guidance scales g[N] (float32, indexed by DDIM index like the coefficient table; DESIGN.md section
+  11).  `guidance_scale` a float: g[i] = it where t_lo <= steps[i] <= t_hi (`guidance_interval`, bounds in training
+  timesteps, inclusive; None = everywhere) and 1 elsewhere.  A sequence of N finite floats: g itself (no interval).
+  A step with g[i] == 1 is unguided."""
+  steps = np.asarray(steps)
+  n = steps.size
+  if np.ndim(guidance_scale) > 0:
+    if guidance_interval is not None:
+      raise ValueError("guidance_interval cannot be given with a sequence guidance_scale: the sequence is the schedule")
+    g = np.asarray(guidance_scale, dtype=np.float64)
+    if g.ndim != 1 or g.size != n:
+      raise ValueError(f"guidance_scale has shape {g.shape}, expected one float or {n} floats (one per DDIM index)")
+  else:
+    g = np.full(n, float(guidance_scale), dtype=np.float64)
+    if guidance_interval is not None:
+      if np.ndim(guidance_interval) != 1 or len(guidance_interval) != 2:
+        raise ValueError(f"guidance_interval must be (t_lo, t_hi), got {guidance_interval!r}")
+      t_lo, t_hi = (float(v) for v in guidance_interval)
+      if not t_lo <= t_hi:
+        raise ValueError(f"guidance_interval: t_lo={t_lo} must not exceed t_hi={t_hi}")
+      g = np.where((steps >= t_lo) & (steps <= t_hi), g, 1.)
+  with np.errstate(over="ignore"):                # (a float64 beyond float32's range becomes inf and is rejected)
+    g = g.astype(np.float32)
+  if not np.all(np.isfinite(g)):
+    raise ValueError("guidance_scale must be finite (as float32)")
+  return g
 
 
 class LatentDiffusionModel(object):
@@ -377,7 +412,7 @@ def deis_weights(lams, lam_target):
 class LatentDiffusionModelSampler(LatentDiffusionModel):
 
   def __init__(self, *args, use_graph=True, verbose=True, temb_table=True, sampler="ddim", noise_source="host",
-               **kwargs):
+               skip_unguided=True, **kwargs):
     super().__init__(*args, **kwargs)
     if sampler not in SAMPLERS:
       raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
@@ -392,8 +427,14 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     self._temb_tbl = None
     self._pre_dec = False
     self._verbose = verbose
+    self._skip_unguided = bool(skip_unguided)    # A/B: False = an unguided step still evaluates all 2B rows
     self._graph = None
     self._graph_key = None
+    self._sched_graphs = {}                      # guidance schedules: form (guided?) -> captured step
+    self._sched_key = None
+    self._gtab = None
+    self._plms_tbl = None
+    self._form_events = None
     self.last_step_ms = None
 
   # ---- the steps' temb projections, once per sampler ---------------------------------
@@ -431,7 +472,12 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       if self._noise_source == "device" and self._rng is None:
         self._rng = torch.zeros(4, dtype=torch.int32, device=dev)    # (written by each loop's reset)
       self._state_key = key
-      self._graph = None
+      self._drop_graphs()
+
+  def _drop_graphs(self):
+    """A buffer the captured steps read has a new address."""
+    self._graph = None
+    self._sched_graphs = {}
 
   def _set_loop_start(self, start_index):
     """PLMS / DEIS: the loop's first step is the one at DDIM index `start_index` (it has no history)."""
@@ -448,7 +494,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     if buf is None or tuple(buf.shape) != tuple(shape):
       buf = torch.empty(shape, dtype=dtype, device=self.device)
       setattr(self, name, buf)
-      self._graph = None
+      self._drop_graphs()
     buf.copy_(src)
     return buf
 
@@ -515,6 +561,120 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
                         dec_index=dec_index and not self._pre_dec, clip_denoised=clip_denoised,
                         noise_index_stride=stride, pred_x0_out=pred_x0_out)
 
+  # ---- guidance schedules ---------------------------------------------
+  def _guidance(self, guidance_scale, guidance_interval):
+    """None for a float scale without an interval (the loops above, untouched); else the schedule's float32 [N] table
+    in the device buffer the sampler owns (its values change in place: the captured steps read it by address)."""
+    if np.ndim(guidance_scale) == 0 and guidance_interval is None:
+      return None
+    g = guidance_table(self._ddim_steps, guidance_scale, guidance_interval)
+    if self._eta != 0:
+      raise ValueError(f"a guidance schedule (a sequence guidance_scale or guidance_interval) needs eta = 0, got "
+                       f"{self._eta}: the scheduled update has no eta noise")
+    if self._gtab is None:
+      self._gtab = torch.empty(len(g), dtype=torch.float32, device=self.device)
+    self._gtab.copy_(torch.from_numpy(g))
+    return g
+
+  def _sched_weights(self):
+    """The weight table of the scheduled update: None (ddim: no history), the Adams-Bashforth constants as a table
+    (plms: row [i][j] = PLMS_WEIGHTS[j]) or multistep_weights() (deis); float32 [N,4,4] on the device."""
+    if self._sampler == "deis":
+      return self._device_ms_weights()
+    if self._sampler == "plms":
+      if self._plms_tbl is None:
+        w = np.zeros((len(self._ddim_steps), 4, 4), dtype=np.float32)
+        for j, row in enumerate(PLMS_WEIGHTS):
+          w[:, j, :j + 1] = np.array(row, dtype=np.float32)
+        self._plms_tbl = torch.from_numpy(w).to(self.device).contiguous()
+      return self._plms_tbl
+    return None
+
+  def _step_sched(self, guided, dec_index, pred_x0_out=None, masked=False, rng=False):
+    """One step of a guidance schedule.  Guided: today's U-Net evaluation on [xt; xt], then the update with the scale
+    gtab[index].  Unguided: the U-Net on the conditional rows x2[B:] against the resident context's rows B .. 2B-1,
+    writing eps[B:] (skip_unguided=False: all 2B rows, as a guided step), then the update on eps[B:] alone.  Either
+    update writes both halves of x2."""
+    B = self._xt.shape[0]
+    if guided or not self._skip_unguided:
+      self._unet.forward(self._x2, steps=self._steps_dev, index=self._index_dev, out=self._eps, paired_rows=True,
+                         **self._temb_kwargs(dec_index))
+    else:
+      self._unet.forward(self._x2[B:], steps=self._steps_dev, index=self._index_dev, out=self._eps[B:],
+                         paired_rows=False, context_rows=(B, 2 * B), **self._temb_kwargs(dec_index))
+    blend = {}
+    if masked:
+      blend = dict(z0=self._z0_buf, mask=self._mask_buf, q_coef=self._device_q_tables()[2])
+      if not rng:
+        blend.update(q_noise=self._q_buf, q_index_stride=self._q_buf[0].numel())
+    hist = {}
+    weights = self._sched_weights()
+    if weights is not None:
+      hist = dict(ring=self._ring, start=self._start, weights=weights)
+    ops.cfg_sched_update(self._eps, self._xt, self._xt, self._coef_dev, self._gtab, self._index_dev, guided,
+                         rng=self._rng if rng else None, x_unet_out=self._x2,
+                         dec_index=dec_index and not self._pre_dec, pred_x0_out=pred_x0_out, **hist, **blend)
+
+  def _sample_loop_sched(self, forms, reset, step, gkey, record):
+    """_sample_loop for a guidance schedule: forms[s] = whether the s-th step of the loop is guided (host-known when
+    the loop starts; the index stays on the device); `step(guided, dec_index)` enqueues one step.  With graphs, one
+    step per form in use is captured once per `gkey` and the host replays whichever form each step takes.  Events
+    around every contiguous run of one form give the per-form times (last_form_ms_per_step)."""
+    num_steps = len(forms)
+    reset()
+    use_graph = self._use_graph and record is None
+    if use_graph:
+      if self._sched_key != gkey:
+        self._sched_graphs, self._sched_key = {}, gkey
+      for guided in sorted(set(forms) - set(self._sched_graphs), reverse=True):
+        self._index_dev.fill_(num_steps - 1)         # (the warm-up step does not move the counter)
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+          step(guided, False)
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        reset()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+          step(guided, True)
+        self._sched_graphs[guided] = g
+        reset()
+    marks = [(torch.cuda.Event(enable_timing=True), None)]
+    marks[0][0].record()
+    for i, guided in enumerate(forms):
+      if use_graph:
+        self._sched_graphs[guided].replay()
+      else:
+        step(guided, True)
+        if record is not None:
+          record.append(self._xt.clone())
+      if i + 1 == num_steps or forms[i + 1] != guided:
+        ev = torch.cuda.Event(enable_timing=True)
+        ev.record()
+        marks.append((ev, guided))
+    self._loop_events = (marks[0][0], marks[-1][0], num_steps)
+    self._form_events = (marks, list(forms))
+
+  def last_form_ms_per_step(self):
+    """{"guided": ms, "unguided": ms} of the last scheduled loop: device time of the contiguous runs of each form
+    divided by its step count (None for a form the loop did not take; synchronises)."""
+    marks, forms = self._form_events
+    marks[-1][0].synchronize()
+    total = {True: 0., False: 0.}
+    for (e0, _), (e1, guided) in zip(marks[:-1], marks[1:]):
+      total[guided] += e0.elapsed_time(e1)
+    count = {True: sum(forms), False: len(forms) - sum(forms)}
+    return {name: (total[k] / count[k] if count[k] else None) for name, k in (("guided", True), ("unguided", False))}
+
+  def _sched_forms(self, g, first, count):
+    """Guided? for the steps at DDIM indices first, first - 1, .. (count of them)."""
+    return [bool(g[i] != 1.) for i in range(first, first - count, -1)]
+
+  def _sched_key_of(self, masked, rng):
+    return ("sched", self._ctx_shape, masked, self._noise_source, rng, self._step_spacing, self._sampler,
+            self._skip_unguided)
+
   def ddim_sample(self, xt, cond, index, guidance_scale=1., clip_denoised=True,
                   return_pred_x0=False, noise=None):
     """model_runners.py:438-472 for a host-side `index`.  `noise` [B,h,w,c] replaces
@@ -571,7 +731,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     if buf is None or tuple(buf.shape) != tuple(shape):
       buf = torch.zeros(shape, dtype=torch.float32, device=self.device)
       setattr(self, name, buf)
-      self._graph = None
+      self._drop_graphs()
     rng = self._set_rng(seed, first_sample_index)
     for i in range(rows):
       ops.normal_fill(buf[i], rng, stream0 + i)
@@ -621,12 +781,15 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     self._loop_events = (t0, t1, num_steps)
 
   def ddim_p_sample_loop(self, cond_model_inputs, shape, guidance_scale=5., x_T=None,
-                         noises=None, seed=0, first_sample_index=0, record=None):
+                         noises=None, seed=0, first_sample_index=0, record=None, guidance_interval=None):
     """model_runners.py:474-509.  Extra inputs the reference lacks: `x_T` [B,h,w,4]
     (else N(0,1) from `seed`, keyed per global sample index), `noises` [N,B,h,w,4]
     indexed by DDIM index (only read when eta > 0), `record` (list: receives x_t
     after every step -- disables graph replay).  noise_source="device": what the caller
-    does not give is drawn on the device; without `noises` no table exists."""
+    does not give is drawn on the device; without `noises` no table exists.
+    `guidance_scale` may be N floats indexed by DDIM index, or a float with `guidance_interval` = (t_lo, t_hi) in
+    training timesteps (guided where t_lo <= steps[i] <= t_hi); DESIGN.md section 11, eta = 0 only."""
+    gsched = self._guidance(guidance_scale, guidance_interval)
     B, h, w, c = (int(s) for s in shape)
     context = self._cond_stage_model(cond_model_inputs)                   # :475
     n = len(self._ddim_steps)
@@ -643,6 +806,11 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       self._index_dev.fill_(self._loop_start_index(n))                    # :476 (index = N - 1 in the first step)
       self._set_loop_start(n - 1)
 
+    if gsched is not None:
+      self._sample_loop_sched(self._sched_forms(gsched, n - 1, n), reset,
+                              lambda guided, dec: self._step_sched(guided, dec, rng=rng),
+                              self._sched_key_of(False, rng), record)
+      return self._finish(self._xt)
     gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, False, self._noise_source, rng,
             self._step_spacing, self._sampler)
     self._sample_loop(n, reset, lambda dec: self._step(guidance_scale, False, noise_table, dec_index=dec, rng=rng),
@@ -686,7 +854,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
 
   def ddim_p_sample_loop_img2img(self, cond_model_inputs, init_images, guidance_scale=5., strength=0.75,
                                  mask=None, encode_noise=None, q_noises=None, noises=None, seed=0,
-                                 first_sample_index=0, record=None):
+                                 first_sample_index=0, record=None, guidance_interval=None):
     """img2img (SDEdit) and masked inpainting on the DDIM loop.
     cond_model_inputs: token ids [uncond x B; cond x B].  init_images [B,H,W,3] (or [H,W,3], tiled) float32
     in [-1, 1].  z0 = get_latents(init_images, encode_noise); k = int(strength * N); the loop starts from
@@ -694,7 +862,9 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     resolution, 1 = keep: before the step at every index i < k-1, x <- m q_sample(z0, steps[i], Q[i]) + (1-m) x.
     `q_noises` [N,B,h,w,c] (Q, indexed by DDIM index; else seed's Q_STREAM + i per global sample index),
     `noises` as in ddim_p_sample_loop, `record` receives x after each of the k steps (eager, no graph).
-    Returns the decoded images; the final latents stay in self._xt."""
+    `guidance_scale` / `guidance_interval` as in ddim_p_sample_loop (the table covers all N indices; the loop walks
+    its first k).  Returns the decoded images; the final latents stay in self._xt."""
+    gsched = self._guidance(guidance_scale, guidance_interval)
     n = len(self._ddim_steps)
     k = img2img_start(strength, n)
     B = len(cond_model_inputs) // 2
@@ -745,6 +915,11 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       self._index_dev.fill_(self._loop_start_index(k))
       self._set_loop_start(k - 1)
 
+    if gsched is not None:
+      self._sample_loop_sched(self._sched_forms(gsched, k - 1, k), reset,
+                              lambda guided, dec: self._step_sched(guided, dec, masked=masked, rng=rng),
+                              self._sched_key_of(masked, rng), record)
+      return self._finish(self._xt)
     gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, masked, self._noise_source, rng,
             self._step_spacing, self._sampler)
     self._sample_loop(k, reset, lambda dec: self._step(guidance_scale, False, noise_table, dec_index=dec,
@@ -753,7 +928,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
 
   def ddim_p_sample_loop_progressive(self, cond_model_inputs, shape, guidance_scale=5.,
                                      record_freq=5, x_T=None, noises=None, seed=0,
-                                     first_sample_index=0):
+                                     first_sample_index=0, guidance_interval=None):
     """Intended semantics of model_runners.py:511-575 (the reference version calls a method
     that does not exist, :535, and returns three values to a caller unpacking two,
     run_ldm_sampler.py:90 -- neither bug is reproduced).  Runs the same loop as
@@ -761,7 +936,8 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     the predicted x0 of the LAST step whose index // record_freq == r (the reference's
     insert_mask overwrites a slot on every such step, :545-553), i.e. of index r*record_freq.
     Returns (images [B,H,W,3], sample_progress [B,R,H,W,3], pred_x0_progress [B,R,H,W,3]),
-    all decoded with decode_first_stage."""
+    all decoded with decode_first_stage.  `guidance_scale` / `guidance_interval` as in ddim_p_sample_loop."""
+    gsched = self._guidance(guidance_scale, guidance_interval)
     B, h, w, c = (int(s) for s in shape)
     context = self._cond_stage_model(cond_model_inputs)
     n = len(self._ddim_steps)
@@ -778,7 +954,10 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     x0_prog = torch.zeros_like(sample_prog)
     pred_x0 = torch.empty_like(self._xt)
     for index in range(n - 1, -1, -1):
-      self._step(guidance_scale, False, noise_table, dec_index=True, pred_x0_out=pred_x0, rng=rng)
+      if gsched is not None:
+        self._step_sched(bool(gsched[index] != 1.), True, pred_x0_out=pred_x0, rng=rng)
+      else:
+        self._step(guidance_scale, False, noise_table, dec_index=True, pred_x0_out=pred_x0, rng=rng)
       r = index // record_freq
       if r < num_records:                      # later (smaller) indices overwrite the slot
         sample_prog[:, r].copy_(self._xt)

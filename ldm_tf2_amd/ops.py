@@ -21,7 +21,7 @@ __all__ = [
     "bmm_nt", "conv3x3_small", "groupnorm", "layernorm", "softmax_rows", "attention",
     "time_embedding", "gemv", "cfg_ddim_update", "cfg_ddim_update_masked", "cfg_plms_update", "q_sample",
     "philox_u32", "normal_fill", "q_sample_rng", "cfg_ddim_update_rng", "cfg_plms_update_rng", "cfg_ms_update",
-    "cfg_ms_update_rng", "post_quant", "vq_nearest", "embedding",
+    "cfg_ms_update_rng", "cfg_sched_update", "post_quant", "vq_nearest", "embedding",
     "minmax_u8", "cast",
 ]
 
@@ -1004,6 +1004,43 @@ def cfg_ms_update_rng(eps_all, xt, xt_out, ring, coef, index, start, weights, rn
       _ptr(start), *_ms_weights(weights, coef), _rng(rng), int(bool(dec_index)), float(guidance_scale), B, n,
       _ptr(_f32(z0, "z0")), _ptr(_f32(mask, "mask")), _ptr(_f32(q_coef, "q_coef")), xt.shape[-1], _stream()),
         "ldm_cfg_ms_update_rng")
+  return xt_out
+
+
+def cfg_sched_update(eps_all, xt, xt_out, coef, gtab, index, guided, ring=None, start=None, weights=None, rng=None,
+                     x_unet_out=None, dec_index=False, pred_x0_out=None, z0=None, mask=None, q_noise=None,
+                     q_coef=None, q_index_stride=0):
+  """CFG by a guidance table + multistep update (include/ldm_hip.h): cfg_ms_update with the
+  scale read from gtab[*index] (float32 [N] on the device).  `guided` False: the step's eps is the conditional half
+  eps_all[B:], the other half is not read.  `weights` None: no history (the DDIM step at sigma = 0; ring and start
+  unused).  `rng`: the blend's Q is drawn in the launch (no q_noise).  Ring, start and the blend as cfg_ms_update."""
+  B = xt.shape[0]
+  n = xt.numel() // B
+  c = xt.shape[-1]
+  assert eps_all.is_contiguous() and eps_all.numel() == 2 * xt.numel()
+  assert gtab.is_contiguous() and gtab.numel() == coef.shape[0]
+  assert index.dtype == torch.int32
+  wp, pitch = None, 0
+  if weights is not None:
+    assert ring.is_contiguous() and ring.numel() == 4 * xt.numel() and start.dtype == torch.int32
+    wp, pitch = _ms_weights(weights, coef)
+  if z0 is not None and rng is not None:
+    _blend_rng(xt, coef, z0, mask, q_coef)
+  elif z0 is not None:
+    assert z0.is_contiguous() and z0.numel() == xt.numel()
+    assert mask.is_contiguous() and mask.numel() * c == xt.numel()
+    assert q_noise.is_contiguous() and q_coef.is_contiguous() and q_coef.shape == (coef.shape[0], 2)
+    assert q_noise.numel() >= (q_coef.shape[0] - 1) * q_index_stride + xt.numel()
+  assert x_unet_out is None or (x_unet_out.is_contiguous() and x_unet_out.numel() == 2 * xt.numel())
+  xd = code(x_unet_out.dtype) if x_unet_out is not None else F32
+  check(lib.ldm_cfg_sched_update(
+      _ptr(_f32(eps_all, "eps_all")), _ptr(_f32(xt, "xt")), _ptr(_f32(ring, "ring")) if weights is not None else None,
+      _ptr(_f32(xt_out, "xt_out")), _ptr(_f32(pred_x0_out, "pred_x0_out")), _ptr(x_unet_out), xd,
+      _ptr(_f32(coef, "coef")), _ptr(_f32(gtab, "gtab")), _ptr(index), _ptr(start) if weights is not None else None,
+      wp, pitch, None if rng is None else _rng(rng), int(bool(guided)), int(bool(dec_index)), B, n,
+      _ptr(_f32(z0, "z0")), _ptr(_f32(mask, "mask")), None if rng is not None else _ptr(_f32(q_noise, "q_noise")),
+      0 if rng is not None else int(q_index_stride), _ptr(_f32(q_coef, "q_coef")), c, _stream()),
+        "ldm_cfg_sched_update")
   return xt_out
 
 

@@ -32,6 +32,11 @@ Step table: optional `ldm_sampling` key `step_spacing`, `uniform` (default: the 
 Noise: optional `ldm_sampling` key `noise_source`, `host` (default: NumPy generators, tables uploaded before the loop)
 or `device` (Philox streams drawn inside the update launches, no tables).  The two sources draw
 different numbers from the same `--seed`.
+
+Guidance schedule: `ldm_sampling.guidance_scale` may be a list of `ldm.num_ddim_steps` floats (one per DDIM index), and
+the optional key `ldm_sampling.guidance_interval: [t_lo, t_hi]` (training timesteps, inclusive) guides only the steps
+inside it; steps whose scale is 1 evaluate the U-Net on the conditional rows alone (needs `ldm.eta` 0; DESIGN.md
+section 11).  Every loop above honours both.
 """
 from __future__ import annotations
 
@@ -115,6 +120,18 @@ def noise_source_name(config):
   return config["ldm_sampling"].get("noise_source", "host")
 
 
+def guidance_kwargs(config):
+  """`ldm_sampling.guidance_interval: [t_lo, t_hi]` as the loops' keyword (nothing when the key is absent; the
+  reference's YAML has no such key).  `ldm_sampling.guidance_scale` itself may be a float or a list (DESIGN.md
+  section 11) and is passed on as it is."""
+  iv = config["ldm_sampling"].get("guidance_interval")
+  if iv is None:
+    return {}
+  if not isinstance(iv, (list, tuple)) or len(iv) != 2:
+    raise ValueError(f"ldm_sampling.guidance_interval must be [t_lo, t_hi], got {iv!r}")
+  return dict(guidance_interval=(iv[0], iv[1]))
+
+
 def sampling_call(config, token_ids, seed):
   """(sampler method name, positional args, kwargs) of the call main() makes for `config`."""
   samp = config["ldm_sampling"]
@@ -128,15 +145,15 @@ def sampling_call(config, token_ids, seed):
     if img.dtype != np.uint8 or img.ndim not in (3, 4) or img.shape[-1] != 3:
       raise ValueError(f"init_image must be uint8 [H,W,3] or [B,H,W,3], got {img.dtype} {img.shape}")
     images = img.astype(np.float32) / np.float32(127.5) - np.float32(1.0)
-    kwargs = dict(strength=float(samp.get("strength", 0.75)), seed=seed)
+    kwargs = dict(strength=float(samp.get("strength", 0.75)), seed=seed, **guidance_kwargs(config))
     if samp.get("mask") is not None:
       pm = np.load(samp["mask"])
       lm = latent_mask(pm, downsampling_factor(config))
       kwargs["mask"] = lm[0] if pm.ndim == 2 else lm          # [h,w]: one mask, tiled over the batch
     return "ddim_p_sample_loop_img2img", (token_ids, images, samp["guidance_scale"]), kwargs
   if samp.get("sample_save_progress"):
-    return "ddim_p_sample_loop_progressive", base, dict(seed=seed)
-  return "ddim_p_sample_loop", base, dict(seed=seed)
+    return "ddim_p_sample_loop_progressive", base, dict(seed=seed, **guidance_kwargs(config))
+  return "ddim_p_sample_loop", base, dict(seed=seed, **guidance_kwargs(config))
 
 
 def build_from_config(config, dtype=torch.bfloat16, device="cuda:0", seed=2, use_graph=True,

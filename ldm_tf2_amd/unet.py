@@ -184,6 +184,7 @@ class UNet:
     self._lane_levels = None if lane_levels is None else int(lane_levels)
     self._lane_state = {}
     self._rows = None                     # a lane's slice of the rows (context K / V^T); None = all rows
+    self._ctx_sel = None                  # the context rows those rows attend to (forward(context_rows=) offsets them)
     self._pend = None
     self._model_channels = model_channels
     self._out_channels = out_channels
@@ -402,7 +403,7 @@ class UNet:
     att, att_full = self._pair_buf("st_att", (R, T, hs), dt, pair)
     ms = fold is not None and st.ms
     ops.attention(qk[..., :hs], qk[..., hs:], vt, att, st.heads, st.sp, scale, matrix_softmax=ms)
-    ctx_k, ctx_vt = (st.ctx_k, st.ctx_vt) if self._rows is None else (st.ctx_k[self._rows], st.ctx_vt[self._rows])
+    ctx_k, ctx_vt = (st.ctx_k, st.ctx_vt) if self._ctx_sel is None else (st.ctx_k[self._ctx_sel], st.ctx_vt[self._ctx_sel])
     Ro = ctx_k.shape[0]                   # rows of `out` (= 2 R for a pair)
     assert Ro == (2 * R if pair else R) and out.shape[0] == Ro
     panel = (fold is not None and st.ffn_aux is not None and self._fused_ffn and Ro * T >= self._ffn_min_rows)
@@ -479,7 +480,7 @@ class UNet:
 
   # ---- forward ---------------------------------------------------------------------------------
   def forward(self, x, t_rows=None, steps=None, index=None, out=None, shared_t=False, paired_rows=False,
-              temb_table=None, pre_decrement=False):
+              temb_table=None, pre_decrement=False, context_rows=None):
     """x f32 [R,h,w,4].  Timestep either per row (`t_rows` int32 [R]) or, for the
     graph-replayed DDIM loop, `steps[*index]` for every row.  `shared_t=True` with
     t_rows declares that all rows carry t_rows[0].
@@ -489,12 +490,21 @@ class UNet:
     -- the first ResBlock and the first transformer block up to its self-attention -- are the same numbers for both
     halves: they run once, on R/2 rows (`shared_prefix`, bf16 and float32).
     `temb_table` (from `temb_table(steps)`) with `index`: the step's temb projections are row *index of that table
-    (one launch instead of four); `pre_decrement`: that launch first decrements *index, the DDIM loop's counter."""
+    (one launch instead of four); `pre_decrement`: that launch first decrements *index, the DDIM loop's counter.
+    `context_rows=(lo, hi)`: x has hi - lo rows and row r attends to row lo + r of the resident context (set_context
+    projected more rows than this evaluation has): the conditional half (B, 2B) of a classifier-free-guidance batch on
+    its own.  The cross-attention launches read contiguous row slices of the projections."""
     assert x.dtype == torch.float32 and x.is_contiguous()
     R, h, w, _ = x.shape
     nlev = max(self.skip_lvl)
     assert h % (1 << nlev) == 0 and w % (1 << nlev) == 0, "latent size must divide by 2**levels"
-    assert self.sts[0].ctx_k is not None and self._ctx_rows == R, "call set_context(context) first"
+    assert self.sts[0].ctx_k is not None, "call set_context(context) first"
+    if context_rows is None:
+      assert self._ctx_rows == R, "call set_context(context) first"
+    else:
+      lo, hi = (int(v) for v in context_rows)
+      assert 0 <= lo and hi <= self._ctx_rows and hi - lo == R, (context_rows, self._ctx_rows, R)
+      assert not paired_rows, "paired_rows needs the whole context"
     if out is None:
       out = torch.empty(R, h, w, self._out_channels, dtype=torch.float32, device=self.device)
     if temb_table is not None:
@@ -505,6 +515,7 @@ class UNet:
       assert not pre_decrement
       tall = self._temb(R, t_rows, steps, index, shared_t)
     env = self._env(x, tall, out)
+    env["ctx_lo"] = None if context_rows is None else int(context_rows[0])
     env["pair"] = bool(paired_rows and self._shared_prefix and R % 2 == 0 and self._lanes == 1
                        and self.in_blocks[0][0] == "res" and self.in_blocks[0][2] is not None)
     prog = env["prog"]
@@ -566,6 +577,12 @@ class UNet:
     x = env["x"]
     nr = x.shape[0] if rows is None else rows.stop - rows.start
     self._rows = rows
+    # the context rows of this segment's rows: all of them, a branch's slice, or offset by forward(context_rows=)
+    lo = env.get("ctx_lo")
+    if lo is None:
+      self._ctx_sel = rows
+    else:
+      self._ctx_sel = slice(lo, lo + nr) if rows is None else slice(lo + rows.start, lo + rows.stop)
     with ops.plan_scope(nr, x.shape[1], self.dtype), ops.workspace_scope(self._ws):
       self._pend = None
       self._gnp = self.buf.get("gn_partial", (nr * 128 * 32 * 2,), torch.float32)
