@@ -34,6 +34,16 @@ static inline int ldm_launch_status(const char* what) {
   return LDM_OK;
 }
 
+#define DT_OK(d) ((d) == LDM_F32 || (d) == LDM_BF16)
+
+// blocks of a grid-stride launch over `total` items
+static inline int grid_for(int64_t total, int per_block = 256, int cap = 4096) {
+  int64_t g = (total + per_block - 1) / per_block;
+  if (g < 1) g = 1;
+  if (g > cap) g = cap;
+  return (int)g;
+}
+
 // ---- scalar conversions ----------------------------------------------------
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 // f32 -> bf16, round-to-nearest-even, NaN stays NaN: gfx950's v_cvt_pk_bf16_f32 converts

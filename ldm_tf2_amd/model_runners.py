@@ -371,8 +371,8 @@ class LatentDiffusionModel(object):
 
 
 # PLMS: row j = Adams-Bashforth weights of (e_i, e_{i+1}, .., e_{i+j}), the guided eps of the
-# step at DDIM index i and of the j steps before it in the loop.  cfg_plms_kernel (csrc/misc.hip) carries the same
-# numbers as (numerators) / denominator.
+# step at DDIM index i and of the j steps before it in the loop.  cfg_update4_kernel<.., kAdamsBashforth, ..>
+# (csrc/sampler.hip) carries the same numbers as (numerators) / denominator.
 PLMS_WEIGHTS = (
     (1.,),
     (3. / 2., -1. / 2.),
@@ -511,55 +511,36 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     # selects the step's row of the temb table), so a loop starts from index = N and ends at 0.
     self._unet.forward(self._x2, steps=self._steps_dev, index=self._index_dev, out=self._eps, paired_rows=True,
                        **self._temb_kwargs(dec_index))
+    rng, multistep = bool(rng), self._sampler in MULTISTEP
+    # (device noise: no tables; multistep: eta = 0, so no noise table either, and the loops never clip)
+    assert noise_table is None or not (rng or multistep)
+    assert not (clip_denoised and multistep)
+    update = {("ddim", False): ops.cfg_ddim_update_masked if masked else ops.cfg_ddim_update,
+              ("ddim", True): ops.cfg_ddim_update_rng,
+              ("plms", False): ops.cfg_plms_update, ("plms", True): ops.cfg_plms_update_rng,
+              ("deis", False): ops.cfg_ms_update, ("deis", True): ops.cfg_ms_update_rng}[self._sampler, rng]
+    kw = dict(coef=self._coef_dev, index=self._index_dev, guidance_scale=guidance_scale, x_unet_out=self._x2,
+              dec_index=dec_index and not self._pre_dec, pred_x0_out=pred_x0_out, **self._blend_kwargs(masked, rng))
+    if multistep:
+      kw.update(ring=self._ring, start=self._start)
+      if self._sampler == "deis":
+        kw.update(weights=self._device_ms_weights())
+    else:
+      kw.update(clip_denoised=clip_denoised)
+      if not rng:
+        kw.update(noise=noise_table, noise_index_stride=0 if noise_table is None else noise_table[0].numel())
     if rng:
-      assert noise_table is None
-      blend = {}
-      if masked:
-        blend = dict(z0=self._z0_buf, mask=self._mask_buf, q_coef=self._device_q_tables()[2])
-      dec = dec_index and not self._pre_dec
-      if self._sampler == "deis":
-        assert not clip_denoised
-        ops.cfg_ms_update_rng(self._eps, self._xt, self._xt, self._ring, self._coef_dev, self._index_dev,
-                              self._start, self._device_ms_weights(), self._rng, guidance_scale, x_unet_out=self._x2,
-                              dec_index=dec, pred_x0_out=pred_x0_out, **blend)
-      elif self._sampler == "plms":
-        assert not clip_denoised
-        ops.cfg_plms_update_rng(self._eps, self._xt, self._xt, self._ring, self._coef_dev, self._index_dev,
-                                self._start, self._rng, guidance_scale, x_unet_out=self._x2, dec_index=dec,
-                                pred_x0_out=pred_x0_out, **blend)
-      else:
-        ops.cfg_ddim_update_rng(self._eps, self._xt, self._xt, self._coef_dev, self._index_dev, self._rng,
-                                guidance_scale, x_unet_out=self._x2, dec_index=dec, clip_denoised=clip_denoised,
-                                pred_x0_out=pred_x0_out, **blend)
-      return
-    if self._sampler in MULTISTEP:
-      # (eta = 0: no noise table; the loops never clip)
-      assert noise_table is None and not clip_denoised
-      blend = {}
-      if masked:
-        blend = dict(z0=self._z0_buf, mask=self._mask_buf, q_noise=self._q_buf, q_coef=self._device_q_tables()[2],
-                     q_index_stride=self._q_buf[0].numel())
-      if self._sampler == "deis":
-        ops.cfg_ms_update(self._eps, self._xt, self._xt, self._ring, self._coef_dev, self._index_dev, self._start,
-                          self._device_ms_weights(), guidance_scale, x_unet_out=self._x2,
-                          dec_index=dec_index and not self._pre_dec, pred_x0_out=pred_x0_out, **blend)
-        return
-      ops.cfg_plms_update(self._eps, self._xt, self._xt, self._ring, self._coef_dev, self._index_dev, self._start,
-                          guidance_scale, x_unet_out=self._x2, dec_index=dec_index and not self._pre_dec,
-                          pred_x0_out=pred_x0_out, **blend)
-      return
-    stride = 0 if noise_table is None else noise_table[0].numel()
-    if masked:
-      ops.cfg_ddim_update_masked(self._eps, self._xt, self._xt, self._coef_dev, self._index_dev, guidance_scale,
-                                 self._z0_buf, self._mask_buf, self._q_buf, self._device_q_tables()[2],
-                                 noise=noise_table, x_unet_out=self._x2, dec_index=dec_index and not self._pre_dec,
-                                 clip_denoised=clip_denoised, noise_index_stride=stride,
-                                 q_index_stride=self._q_buf[0].numel(), pred_x0_out=pred_x0_out)
-      return
-    ops.cfg_ddim_update(self._eps, self._xt, self._xt, self._coef_dev, self._index_dev,
-                        guidance_scale, noise=noise_table, x_unet_out=self._x2,
-                        dec_index=dec_index and not self._pre_dec, clip_denoised=clip_denoised,
-                        noise_index_stride=stride, pred_x0_out=pred_x0_out)
+      kw.update(rng=self._rng)
+    update(self._eps, self._xt, self._xt, **kw)
+
+  def _blend_kwargs(self, masked, rng):
+    """The inpainting blend's arguments of an update: none unless `masked`; the Q table unless Q is drawn (`rng`)."""
+    if not masked:
+      return {}
+    blend = dict(z0=self._z0_buf, mask=self._mask_buf, q_coef=self._device_q_tables()[2])
+    if not rng:
+      blend.update(q_noise=self._q_buf, q_index_stride=self._q_buf[0].numel())
+    return blend
 
   # ---- guidance schedules (DESIGN.md section 11) ---------------------------------------------
   def _guidance(self, guidance_scale, guidance_interval):
@@ -602,18 +583,14 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     else:
       self._unet.forward(self._x2[B:], steps=self._steps_dev, index=self._index_dev, out=self._eps[B:],
                          paired_rows=False, context_rows=(B, 2 * B), **self._temb_kwargs(dec_index))
-    blend = {}
-    if masked:
-      blend = dict(z0=self._z0_buf, mask=self._mask_buf, q_coef=self._device_q_tables()[2])
-      if not rng:
-        blend.update(q_noise=self._q_buf, q_index_stride=self._q_buf[0].numel())
     hist = {}
     weights = self._sched_weights()
     if weights is not None:
       hist = dict(ring=self._ring, start=self._start, weights=weights)
     ops.cfg_sched_update(self._eps, self._xt, self._xt, self._coef_dev, self._gtab, self._index_dev, guided,
                          rng=self._rng if rng else None, x_unet_out=self._x2,
-                         dec_index=dec_index and not self._pre_dec, pred_x0_out=pred_x0_out, **hist, **blend)
+                         dec_index=dec_index and not self._pre_dec, pred_x0_out=pred_x0_out, **hist,
+                         **self._blend_kwargs(masked, rng))
 
   def _sample_loop_sched(self, forms, reset, step, gkey, record):
     """_sample_loop for a guidance schedule: forms[s] = whether the s-th step of the loop is guided (host-known when

@@ -789,19 +789,42 @@ def gemv(x, wt, bias, y, act_in=ACT_NONE, act_out=ACT_NONE):
   return y
 
 
+def _update_dims(xt, index, x_unet_out, ring=None, start=None):
+  """The asserts every cfg_*_update wrapper shares -> (B, n_per_sample, the dtype code of x_unet_out)."""
+  B = xt.shape[0]
+  assert index.dtype == torch.int32
+  if ring is not None:
+    assert ring.is_contiguous() and ring.numel() == 4 * xt.numel() and start.dtype == torch.int32
+  return B, xt.numel() // B, code(x_unet_out.dtype) if x_unet_out is not None else F32
+
+
+def _update_ptrs(eps_all, xt, mid, xt_out, pred_x0_out, x_unet_out, xd, coef, index):
+  """The leading arguments of every ldm_cfg_*_update; `mid`: what the entry has between xt and xt_out."""
+  return (_ptr(_f32(eps_all, "eps_all")), _ptr(_f32(xt, "xt")), *mid, _ptr(_f32(xt_out, "xt_out")),
+          _ptr(_f32(pred_x0_out, "pred_x0_out")), _ptr(x_unet_out), xd, _ptr(_f32(coef, "coef")), _ptr(index))
+
+
+def _blend_args(xt, coef, z0, mask, q_coef, q_noise=None, q_index_stride=0, table=True, q_slots=True):
+  """The inpainting blend's asserts and trailing arguments (z0, mask, [q_noise, q_index_stride,] q_coef, channels).
+  `table`: Q is read from q_noise (else drawn in the launch); `q_slots`: the entry has the two q_noise arguments."""
+  if z0 is not None:
+    assert z0.is_contiguous() and z0.numel() == xt.numel()
+    assert mask.is_contiguous() and mask.numel() * xt.shape[-1] == xt.numel()
+    assert q_coef.is_contiguous() and q_coef.shape == (coef.shape[0], 2)
+    if table:
+      assert q_noise.is_contiguous() and q_noise.numel() >= (q_coef.shape[0] - 1) * q_index_stride + xt.numel()
+  q = () if not q_slots else (_ptr(_f32(q_noise, "q_noise")), int(q_index_stride)) if table else (None, 0)
+  return (_ptr(_f32(z0, "z0")), _ptr(_f32(mask, "mask")), *q, _ptr(_f32(q_coef, "q_coef")), xt.shape[-1])
+
+
 def cfg_ddim_update(eps_all, xt, xt_out, coef, index, guidance_scale, noise=None, x_unet_out=None,
                     dec_index=False, clip_denoised=False, noise_index_stride=0, pred_x0_out=None):
-  B = xt.shape[0]
-  n = xt.numel() // B
-  xd = code(x_unet_out.dtype) if x_unet_out is not None else F32
-  check(lib.ldm_cfg_ddim_update(_ptr(_f32(eps_all, "eps_all")), _ptr(_f32(xt, "xt")),
-                                _ptr(_f32(noise, "noise")), int(noise_index_stride),
-                                _ptr(_f32(xt_out, "xt_out")), _ptr(_f32(pred_x0_out, "pred_x0_out")),
-                                _ptr(x_unet_out), xd, _ptr(_f32(coef, "coef")), _ptr(index),
-                                int(bool(dec_index)), float(guidance_scale),
-                                int(bool(clip_denoised)), B, n, _stream()), "ldm_cfg_ddim_update")
+  B, n, xd = _update_dims(xt, index, x_unet_out)
+  check(lib.ldm_cfg_ddim_update(
+      *_update_ptrs(eps_all, xt, (_ptr(_f32(noise, "noise")), int(noise_index_stride)), xt_out, pred_x0_out,
+                    x_unet_out, xd, coef, index),
+      int(bool(dec_index)), float(guidance_scale), int(bool(clip_denoised)), B, n, _stream()), "ldm_cfg_ddim_update")
   return xt_out
-
 
 
 def cfg_ddim_update_masked(eps_all, xt, xt_out, coef, index, guidance_scale, z0, mask, q_noise, q_coef,
@@ -809,20 +832,12 @@ def cfg_ddim_update_masked(eps_all, xt, xt_out, coef, index, guidance_scale, z0,
                            q_index_stride=0, pred_x0_out=None):
   """cfg_ddim_update, then (at *index = idx >= 1) o <- m * q_sample(z0, steps[idx-1], Q[idx-1]) + (1 - m) * o:
   z0 [B,h,w,c], mask [B,h,w] (1 = keep the init image), Q row j at q_noise + j * q_index_stride, q_coef [N,2]."""
-  B = xt.shape[0]
-  n = xt.numel() // B
-  c = xt.shape[-1]
-  assert z0.is_contiguous() and z0.numel() == xt.numel()
-  assert mask.is_contiguous() and mask.numel() * c == xt.numel()
-  assert q_noise.is_contiguous() and q_coef.is_contiguous() and q_coef.shape == (coef.shape[0], 2)
-  assert q_noise.numel() >= (q_coef.shape[0] - 1) * q_index_stride + xt.numel()
-  xd = code(x_unet_out.dtype) if x_unet_out is not None else F32
+  B, n, xd = _update_dims(xt, index, x_unet_out)
   check(lib.ldm_cfg_ddim_update_masked(
-      _ptr(_f32(eps_all, "eps_all")), _ptr(_f32(xt, "xt")), _ptr(_f32(noise, "noise")), int(noise_index_stride),
-      _ptr(_f32(xt_out, "xt_out")), _ptr(_f32(pred_x0_out, "pred_x0_out")), _ptr(x_unet_out), xd,
-      _ptr(_f32(coef, "coef")), _ptr(index), int(bool(dec_index)), float(guidance_scale), int(bool(clip_denoised)),
-      B, n, _ptr(_f32(z0, "z0")), _ptr(_f32(mask, "mask")), _ptr(_f32(q_noise, "q_noise")), int(q_index_stride),
-      _ptr(_f32(q_coef, "q_coef")), c, _stream()), "ldm_cfg_ddim_update_masked")
+      *_update_ptrs(eps_all, xt, (_ptr(_f32(noise, "noise")), int(noise_index_stride)), xt_out, pred_x0_out,
+                    x_unet_out, xd, coef, index),
+      int(bool(dec_index)), float(guidance_scale), int(bool(clip_denoised)), B, n,
+      *_blend_args(xt, coef, z0, mask, q_coef, q_noise, q_index_stride), _stream()), "ldm_cfg_ddim_update_masked")
   return xt_out
 
 
@@ -832,23 +847,11 @@ def cfg_plms_update(eps_all, xt, xt_out, ring, coef, index, start, guidance_scal
   Adams-Bashforth combination of this step's guided eps and the min(*start - *index, 3) before it.  ring
   [4,B,...] float32 (slot *index & 3 is written, the next j slots are read), start int32 [1] on the device.
   `z0` (with mask [B,h,w], q_noise, q_coef [N,2]): the inpainting blend of cfg_ddim_update_masked, same launch."""
-  B = xt.shape[0]
-  n = xt.numel() // B
-  c = xt.shape[-1]
-  assert ring.is_contiguous() and ring.numel() == 4 * xt.numel()
-  assert index.dtype == torch.int32 and start.dtype == torch.int32
-  if z0 is not None:
-    assert z0.is_contiguous() and z0.numel() == xt.numel()
-    assert mask.is_contiguous() and mask.numel() * c == xt.numel()
-    assert q_noise.is_contiguous() and q_coef.is_contiguous() and q_coef.shape == (coef.shape[0], 2)
-    assert q_noise.numel() >= (q_coef.shape[0] - 1) * q_index_stride + xt.numel()
-  xd = code(x_unet_out.dtype) if x_unet_out is not None else F32
+  B, n, xd = _update_dims(xt, index, x_unet_out, ring, start)
   check(lib.ldm_cfg_plms_update(
-      _ptr(_f32(eps_all, "eps_all")), _ptr(_f32(xt, "xt")), _ptr(_f32(ring, "ring")), _ptr(_f32(xt_out, "xt_out")),
-      _ptr(_f32(pred_x0_out, "pred_x0_out")), _ptr(x_unet_out), xd, _ptr(_f32(coef, "coef")), _ptr(index),
-      _ptr(start), int(bool(dec_index)), float(guidance_scale), B, n, _ptr(_f32(z0, "z0")),
-      _ptr(_f32(mask, "mask")), _ptr(_f32(q_noise, "q_noise")), int(q_index_stride), _ptr(_f32(q_coef, "q_coef")),
-      c, _stream()), "ldm_cfg_plms_update")
+      *_update_ptrs(eps_all, xt, (_ptr(_f32(ring, "ring")),), xt_out, pred_x0_out, x_unet_out, xd, coef, index),
+      _ptr(start), int(bool(dec_index)), float(guidance_scale), B, n,
+      *_blend_args(xt, coef, z0, mask, q_coef, q_noise, q_index_stride), _stream()), "ldm_cfg_plms_update")
   return xt_out
 
 
@@ -917,43 +920,26 @@ def q_sample_rng(x0, rng, stream_word, t, sqrt_alphas_cumprod, sqrt_one_minus_al
   return xt_out
 
 
-def _blend_rng(xt, coef, z0, mask, q_coef):
-  if z0 is not None:
-    assert z0.is_contiguous() and z0.numel() == xt.numel()
-    assert mask.is_contiguous() and mask.numel() * xt.shape[-1] == xt.numel()
-    assert q_coef.is_contiguous() and q_coef.shape == (coef.shape[0], 2)
-
-
 def cfg_ddim_update_rng(eps_all, xt, xt_out, coef, index, rng, guidance_scale, x_unet_out=None, dec_index=False,
                         clip_denoised=False, pred_x0_out=None, z0=None, mask=None, q_coef=None):
   """cfg_ddim_update / cfg_ddim_update_masked (`z0`, mask [B,h,w], q_coef [N,2]) with the eta noise and the blend's
   Q drawn in the launch from `rng` (streams ETA_STREAM + *index, Q_STREAM + *index - 1): no tables."""
-  B = xt.shape[0]
-  n = xt.numel() // B
-  _blend_rng(xt, coef, z0, mask, q_coef)
-  xd = code(x_unet_out.dtype) if x_unet_out is not None else F32
+  B, n, xd = _update_dims(xt, index, x_unet_out)
   check(lib.ldm_cfg_ddim_update_rng(
-      _ptr(_f32(eps_all, "eps_all")), _ptr(_f32(xt, "xt")), _rng(rng), _ptr(_f32(xt_out, "xt_out")),
-      _ptr(_f32(pred_x0_out, "pred_x0_out")), _ptr(x_unet_out), xd, _ptr(_f32(coef, "coef")), _ptr(index),
-      int(bool(dec_index)), float(guidance_scale), int(bool(clip_denoised)), B, n, _ptr(_f32(z0, "z0")),
-      _ptr(_f32(mask, "mask")), _ptr(_f32(q_coef, "q_coef")), xt.shape[-1], _stream()), "ldm_cfg_ddim_update_rng")
+      *_update_ptrs(eps_all, xt, (_rng(rng),), xt_out, pred_x0_out, x_unet_out, xd, coef, index),
+      int(bool(dec_index)), float(guidance_scale), int(bool(clip_denoised)), B, n,
+      *_blend_args(xt, coef, z0, mask, q_coef, table=False, q_slots=False), _stream()), "ldm_cfg_ddim_update_rng")
   return xt_out
 
 
 def cfg_plms_update_rng(eps_all, xt, xt_out, ring, coef, index, start, rng, guidance_scale, x_unet_out=None,
                         dec_index=False, pred_x0_out=None, z0=None, mask=None, q_coef=None):
   """cfg_plms_update with the blend's Q drawn in the launch from `rng` (stream Q_STREAM + *index - 1)."""
-  B = xt.shape[0]
-  n = xt.numel() // B
-  assert ring.is_contiguous() and ring.numel() == 4 * xt.numel()
-  assert index.dtype == torch.int32 and start.dtype == torch.int32
-  _blend_rng(xt, coef, z0, mask, q_coef)
-  xd = code(x_unet_out.dtype) if x_unet_out is not None else F32
+  B, n, xd = _update_dims(xt, index, x_unet_out, ring, start)
   check(lib.ldm_cfg_plms_update_rng(
-      _ptr(_f32(eps_all, "eps_all")), _ptr(_f32(xt, "xt")), _ptr(_f32(ring, "ring")), _ptr(_f32(xt_out, "xt_out")),
-      _ptr(_f32(pred_x0_out, "pred_x0_out")), _ptr(x_unet_out), xd, _ptr(_f32(coef, "coef")), _ptr(index),
-      _ptr(start), _rng(rng), int(bool(dec_index)), float(guidance_scale), B, n, _ptr(_f32(z0, "z0")),
-      _ptr(_f32(mask, "mask")), _ptr(_f32(q_coef, "q_coef")), xt.shape[-1], _stream()), "ldm_cfg_plms_update_rng")
+      *_update_ptrs(eps_all, xt, (_ptr(_f32(ring, "ring")),), xt_out, pred_x0_out, x_unet_out, xd, coef, index),
+      _ptr(start), _rng(rng), int(bool(dec_index)), float(guidance_scale), B, n,
+      *_blend_args(xt, coef, z0, mask, q_coef, table=False, q_slots=False), _stream()), "ldm_cfg_plms_update_rng")
   return xt_out
 
 
@@ -969,41 +955,22 @@ def cfg_ms_update(eps_all, xt, xt_out, ring, coef, index, start, weights, guidan
   """CFG + table-weighted multistep update (include/ldm_hip.h): cfg_plms_update with the weights of the step at
   *index with j = min(*start - *index, 3) earlier steps read from weights[*index, j, :j + 1] (float32 [N,4,4] on the
   device) instead of the Adams-Bashforth constants.  Ring, start and the blend as cfg_plms_update."""
-  B = xt.shape[0]
-  n = xt.numel() // B
-  c = xt.shape[-1]
-  assert ring.is_contiguous() and ring.numel() == 4 * xt.numel()
-  assert index.dtype == torch.int32 and start.dtype == torch.int32
-  if z0 is not None:
-    assert z0.is_contiguous() and z0.numel() == xt.numel()
-    assert mask.is_contiguous() and mask.numel() * c == xt.numel()
-    assert q_noise.is_contiguous() and q_coef.is_contiguous() and q_coef.shape == (coef.shape[0], 2)
-    assert q_noise.numel() >= (q_coef.shape[0] - 1) * q_index_stride + xt.numel()
-  xd = code(x_unet_out.dtype) if x_unet_out is not None else F32
+  B, n, xd = _update_dims(xt, index, x_unet_out, ring, start)
   check(lib.ldm_cfg_ms_update(
-      _ptr(_f32(eps_all, "eps_all")), _ptr(_f32(xt, "xt")), _ptr(_f32(ring, "ring")), _ptr(_f32(xt_out, "xt_out")),
-      _ptr(_f32(pred_x0_out, "pred_x0_out")), _ptr(x_unet_out), xd, _ptr(_f32(coef, "coef")), _ptr(index),
+      *_update_ptrs(eps_all, xt, (_ptr(_f32(ring, "ring")),), xt_out, pred_x0_out, x_unet_out, xd, coef, index),
       _ptr(start), *_ms_weights(weights, coef), int(bool(dec_index)), float(guidance_scale), B, n,
-      _ptr(_f32(z0, "z0")), _ptr(_f32(mask, "mask")), _ptr(_f32(q_noise, "q_noise")), int(q_index_stride),
-      _ptr(_f32(q_coef, "q_coef")), c, _stream()), "ldm_cfg_ms_update")
+      *_blend_args(xt, coef, z0, mask, q_coef, q_noise, q_index_stride), _stream()), "ldm_cfg_ms_update")
   return xt_out
 
 
 def cfg_ms_update_rng(eps_all, xt, xt_out, ring, coef, index, start, weights, rng, guidance_scale, x_unet_out=None,
                       dec_index=False, pred_x0_out=None, z0=None, mask=None, q_coef=None):
   """cfg_ms_update with the blend's Q drawn in the launch from `rng` (stream Q_STREAM + *index - 1)."""
-  B = xt.shape[0]
-  n = xt.numel() // B
-  assert ring.is_contiguous() and ring.numel() == 4 * xt.numel()
-  assert index.dtype == torch.int32 and start.dtype == torch.int32
-  _blend_rng(xt, coef, z0, mask, q_coef)
-  xd = code(x_unet_out.dtype) if x_unet_out is not None else F32
+  B, n, xd = _update_dims(xt, index, x_unet_out, ring, start)
   check(lib.ldm_cfg_ms_update_rng(
-      _ptr(_f32(eps_all, "eps_all")), _ptr(_f32(xt, "xt")), _ptr(_f32(ring, "ring")), _ptr(_f32(xt_out, "xt_out")),
-      _ptr(_f32(pred_x0_out, "pred_x0_out")), _ptr(x_unet_out), xd, _ptr(_f32(coef, "coef")), _ptr(index),
+      *_update_ptrs(eps_all, xt, (_ptr(_f32(ring, "ring")),), xt_out, pred_x0_out, x_unet_out, xd, coef, index),
       _ptr(start), *_ms_weights(weights, coef), _rng(rng), int(bool(dec_index)), float(guidance_scale), B, n,
-      _ptr(_f32(z0, "z0")), _ptr(_f32(mask, "mask")), _ptr(_f32(q_coef, "q_coef")), xt.shape[-1], _stream()),
-        "ldm_cfg_ms_update_rng")
+      *_blend_args(xt, coef, z0, mask, q_coef, table=False, q_slots=False), _stream()), "ldm_cfg_ms_update_rng")
   return xt_out
 
 
@@ -1014,32 +981,18 @@ def cfg_sched_update(eps_all, xt, xt_out, coef, gtab, index, guided, ring=None, 
   scale read from gtab[*index] (float32 [N] on the device).  `guided` False: the step's eps is the conditional half
   eps_all[B:], the other half is not read.  `weights` None: no history (the DDIM step at sigma = 0; ring and start
   unused).  `rng`: the blend's Q is drawn in the launch (no q_noise).  Ring, start and the blend as cfg_ms_update."""
-  B = xt.shape[0]
-  n = xt.numel() // B
-  c = xt.shape[-1]
+  if weights is None:
+    ring = start = None
+  B, n, xd = _update_dims(xt, index, x_unet_out, ring, start)
   assert eps_all.is_contiguous() and eps_all.numel() == 2 * xt.numel()
   assert gtab.is_contiguous() and gtab.numel() == coef.shape[0]
-  assert index.dtype == torch.int32
-  wp, pitch = None, 0
-  if weights is not None:
-    assert ring.is_contiguous() and ring.numel() == 4 * xt.numel() and start.dtype == torch.int32
-    wp, pitch = _ms_weights(weights, coef)
-  if z0 is not None and rng is not None:
-    _blend_rng(xt, coef, z0, mask, q_coef)
-  elif z0 is not None:
-    assert z0.is_contiguous() and z0.numel() == xt.numel()
-    assert mask.is_contiguous() and mask.numel() * c == xt.numel()
-    assert q_noise.is_contiguous() and q_coef.is_contiguous() and q_coef.shape == (coef.shape[0], 2)
-    assert q_noise.numel() >= (q_coef.shape[0] - 1) * q_index_stride + xt.numel()
   assert x_unet_out is None or (x_unet_out.is_contiguous() and x_unet_out.numel() == 2 * xt.numel())
-  xd = code(x_unet_out.dtype) if x_unet_out is not None else F32
+  *head, idx = _update_ptrs(eps_all, xt, (_ptr(_f32(ring, "ring")),), xt_out, pred_x0_out, x_unet_out, xd, coef, index)
+  wp = _ms_weights(weights, coef) if weights is not None else (None, 0)
   check(lib.ldm_cfg_sched_update(
-      _ptr(_f32(eps_all, "eps_all")), _ptr(_f32(xt, "xt")), _ptr(_f32(ring, "ring")) if weights is not None else None,
-      _ptr(_f32(xt_out, "xt_out")), _ptr(_f32(pred_x0_out, "pred_x0_out")), _ptr(x_unet_out), xd,
-      _ptr(_f32(coef, "coef")), _ptr(_f32(gtab, "gtab")), _ptr(index), _ptr(start) if weights is not None else None,
-      wp, pitch, None if rng is None else _rng(rng), int(bool(guided)), int(bool(dec_index)), B, n,
-      _ptr(_f32(z0, "z0")), _ptr(_f32(mask, "mask")), None if rng is not None else _ptr(_f32(q_noise, "q_noise")),
-      0 if rng is not None else int(q_index_stride), _ptr(_f32(q_coef, "q_coef")), c, _stream()),
+      *head, _ptr(_f32(gtab, "gtab")), idx, _ptr(start), *wp, None if rng is None else _rng(rng), int(bool(guided)),
+      int(bool(dec_index)), B, n,
+      *_blend_args(xt, coef, z0, mask, q_coef, q_noise, q_index_stride, table=rng is None), _stream()),
         "ldm_cfg_sched_update")
   return xt_out
 
