@@ -307,13 +307,16 @@ __global__ __launch_bounds__(256) void vq_nearest_kernel(const float* __restrict
   float zi[8];
   float zz = 0.f;
   for (int i = 0; i < C; ++i) { zi[i] = z[row * C + i]; zz += zi[i] * zi[i]; }
+  // (INFINITY, no row) is what a lane beyond V keeps.  Every other lane takes its first row (v == lane) whatever its
+  // distance: when no distance is below INFINITY (|z|^2 overflows) the lanes still hold rows, and the reduce below
+  // ends at the lowest of them, row 0, as argmin gives.
   float best = INFINITY;
   int bidx = 0x7fffffff;
   for (int v = lane; v < V; v += 64) {
     float ee = 0.f, ze = 0.f;
     for (int i = 0; i < C; ++i) { const float e = cb[(int64_t)v * C + i]; ee += e * e; ze += zi[i] * e; }
     const float d = zz + ee - 2.0f * ze;   // quantize.py:66-70
-    if (d < best) { best = d; bidx = v; }
+    if (v == lane || d < best) { best = d; bidx = v; }
   }
   // argmin with lowest-index tie break (tf.argmin returns the first minimum)
 #pragma unroll
@@ -322,6 +325,9 @@ __global__ __launch_bounds__(256) void vq_nearest_kernel(const float* __restrict
     const int oi = __shfl_xor(bidx, o, 64);
     if (ob < best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
   }
+  // lane 0 owns row 0, so it always holds a row of the codebook; every lane gathers with ITS index (a NaN distance
+  // compares false both ways and could leave an empty lane without one)
+  bidx = __shfl(bidx, 0, 64);
   if (lane < C) {
     const float zv = z[row * C + lane];
     const float q = cb[(int64_t)bidx * C + lane];
