@@ -528,6 +528,31 @@ int ldm_cfg_sched_update(const float* eps_all, const float* xt, float* ring, flo
                          const float* q_noise, int64_t q_index_stride, const float* q_coef, int channels,
                          void* stream);
 
+/*
+ * Panorama sampling.  A canvas [B][H][W][c] float32 is covered by nW = nY * nX windows of
+ * h x w at stride (sy, sx).  Along an axis of extent L with window l and stride s (1 <= l <= L, 1 <= s <= l):
+ *   n = ceil((L - l) / s) + 1,  origin_i = min(i * s, L - l)    (the last window is clamped to the edge);
+ * window k = ky * nX + kx has origin (oy[ky], ox[kx]).  Both entries compute the origins in the kernel from
+ * (H, h, sy) and (W, w, sx): there is no device table.
+ *
+ * ldm_window_gather: x_win [2][B][nW][h][w][c] in x_dtype, x_win[half][b][k][y][x][:] =
+ * canvas[b][oy + y][ox + x][:] for both halves (the U-Net's [uncond ; cond] rows carry the same x); a bf16 value is
+ * the round-to-nearest-even conversion the update entries' x_unet_out takes.
+ *
+ * ldm_window_fold: eps_win [halves][B][nW][h][w][c] float32 -> eps_canvas [halves][B][H][W][c] float32, halves 1 or
+ * 2: eps_canvas[..][y][x][ch] = (sum of eps_win over the windows covering (y, x)) / count, the sum in float32 in
+ * ascending k starting from the first covering value, the division by (float)count correctly rounded.  A thread owns
+ * a canvas pixel and reads its windows: no atomics, the result is deterministic; count = 1 copies the bits.
+ *
+ * c % 4 == 0 with 16-byte aligned pointers (8-byte for a bf16 x_win) moves one channel quad per thread in 16-byte
+ * accesses; any other c >= 1, or a pointer aligned to its element only, takes an element-wise path with the same
+ * results.  LDM_ERR_ARG: a null pointer, a bad dtype or halves, B, c < 1, h > H, w > W, or a stride outside [1, window].
+ */
+int ldm_window_gather(const float* canvas, void* x_win, int x_dtype, int B, int H, int W, int c, int h, int w, int sy,
+                      int sx, void* stream);
+int ldm_window_fold(const float* eps_win, float* eps_canvas, int halves, int B, int H, int W, int c, int h, int w,
+                    int sy, int sx, void* stream);
+
 /* decode_first_stage prologue (model_runners.py:426 + autoencoder.py:362,434):
  * out = Dense_{C->C}(latents / scale_factor), C <= 8; float32 in, out_dtype out. */
 int ldm_post_quant(const float* latents, float scale_factor, const float* kernel_io,

@@ -1,0 +1,154 @@
+// Panorama sampling: the two kernels a step adds around the U-Net.  A canvas [B][H][W][c] is
+// covered by nY x nX windows of h x w at stride (sy, sx), the last one of an axis clamped to the edge:
+//   n = ceil((L - l) / s) + 1,  origin_i = min(i * s, L - l).
+// ldm_window_gather crops the canvas into the U-Net's window batch, ldm_window_fold averages the windows' eps back
+// onto the canvas.  Origins are recomputed in the kernels: no table, nothing a captured graph could find stale.
+#include "common.h"
+
+namespace {
+
+struct Grid1 {
+  int L, l, s, n;      // canvas extent, window extent, stride, windows
+};
+inline Grid1 grid1(int L, int l, int s) { return Grid1{L, l, s, (L - l + s - 1) / s + 1}; }
+__device__ __forceinline__ int origin(const Grid1& g, int i) {
+  const int o = i * g.s, last = g.L - g.l;
+  return o < last ? o : last;
+}
+// The windows covering position p: indices lo .. hi.  Unclamped windows i cover p iff i*s <= p < i*s + l; the clamped
+// last one starts at L - l <= (n-1)*s, so it covers every p >= L - l, and no p below that reaches index n - 1.
+__device__ __forceinline__ void covering(const Grid1& g, int p, int& lo, int& hi) {
+  lo = p < g.l ? 0 : (p - g.l) / g.s + 1;
+  hi = p >= g.L - g.l ? g.n - 1 : p / g.s;
+}
+
+__device__ __forceinline__ void st4(float* p, const f32x4& v) { *(f32x4*)p = v; }
+__device__ __forceinline__ void st4(bf16_t* p, const f32x4& v) {
+  u32x2 c;
+  c[0] = pack_bf2(v[0], v[1]);
+  c[1] = pack_bf2(v[2], v[3]);
+  *(u32x2*)p = c;
+}
+
+// x_win[half][b][k][y][x][:] = canvas[b][oy(k) + y][ox(k) + x][:] for both halves.  V = 4: a thread moves one channel
+// quad (c % 4 == 0, aligned pointers); V = 1: one element.
+template <typename TX, int V>
+__global__ __launch_bounds__(256) void window_gather_kernel(const float* __restrict__ canvas, TX* __restrict__ x_win,
+                                                            int B, int c, Grid1 gy, Grid1 gx) {
+  const int cv = c / V;
+  const int64_t half = (int64_t)B * gy.n * gx.n * gy.l * gx.l * c;
+  const int64_t total = half / V;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    int64_t r = i;
+    const int ch = (int)(r % cv) * V; r /= cv;
+    const int x = (int)(r % gx.l); r /= gx.l;
+    const int y = (int)(r % gy.l); r /= gy.l;
+    const int kx = (int)(r % gx.n); r /= gx.n;
+    const int ky = (int)(r % gy.n); r /= gy.n;          // r = b
+    const int64_t src = ((r * gy.L + origin(gy, ky) + y) * gx.L + origin(gx, kx) + x) * c + ch;
+    if constexpr (V == 4) {
+      const f32x4 v = *(const f32x4*)(canvas + src);
+      st4(x_win + i * 4, v);
+      st4(x_win + half + i * 4, v);
+    } else {
+      const float v = canvas[src];
+      Elem<TX>::st(x_win + i, v);
+      Elem<TX>::st(x_win + half + i, v);
+    }
+  }
+}
+
+// eps_canvas[b][y][x][:] = (sum over the windows covering (y, x), ascending k = ky * nX + kx, starting from the first
+// covering value) / count, in float32 with a correctly rounded division.  b runs over halves * B canvases.  A thread
+// owns a canvas pixel's channel quad (V = 4) or element (V = 1) and reads the windows: no atomics.
+template <int V>
+__global__ __launch_bounds__(256) void window_fold_kernel(const float* __restrict__ eps_win,
+                                                          float* __restrict__ eps_canvas, int BB, int c, Grid1 gy,
+                                                          Grid1 gx) {
+  const int cv = c / V;
+  const int64_t total = (int64_t)BB * gy.L * gx.L * cv;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    int64_t r = i;
+    const int ch = (int)(r % cv) * V; r /= cv;
+    const int x = (int)(r % gx.L); r /= gx.L;
+    const int y = (int)(r % gy.L); r /= gy.L;           // r = b
+    int ky0, ky1, kx0, kx1;
+    covering(gy, y, ky0, ky1);
+    covering(gx, x, kx0, kx1);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    bool first = true;
+    for (int ky = ky0; ky <= ky1; ++ky) {
+      const int wy = y - origin(gy, ky);
+      for (int kx = kx0; kx <= kx1; ++kx) {
+        const int wx = x - origin(gx, kx);
+        const int64_t src = ((((r * gy.n + ky) * gx.n + kx) * gy.l + wy) * gx.l + wx) * c + ch;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (V == 4) v = *(const f32x4*)(eps_win + src);
+        else v[0] = eps_win[src];
+        acc = first ? v : acc + v;
+        first = false;
+      }
+    }
+    const float count = (float)((ky1 - ky0 + 1) * (kx1 - kx0 + 1));
+    if constexpr (V == 4) {
+      f32x4 o;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[k] = __fdiv_rn(acc[k], count);
+      *(f32x4*)(eps_canvas + i * 4) = o;
+    } else {
+      eps_canvas[i] = __fdiv_rn(acc[0], count);
+    }
+  }
+}
+
+inline bool al(const void* p, int bytes) { return (uintptr_t)p % bytes == 0; }
+
+int grid_check(const char* what, int B, int H, int W, int c, int h, int w, int sy, int sx) {
+  LDM_CHECK_ARG(B > 0 && c > 0 && H > 0 && W > 0, "%s: bad args (B=%d, H=%d, W=%d, c=%d)", what, B, H, W, c);
+  LDM_CHECK_ARG(h >= 1 && h <= H && w >= 1 && w <= W, "%s: window %dx%d must lie within the canvas %dx%d", what, h, w,
+                H, W);
+  LDM_CHECK_ARG(sy >= 1 && sy <= h && sx >= 1 && sx <= w,
+                "%s: stride (%d, %d) must be at least 1 and at most the window (%d, %d)", what, sy, sx, h, w);
+  return LDM_OK;
+}
+
+}  // namespace
+
+extern "C" int ldm_window_gather(const float* canvas, void* x_win, int x_dtype, int B, int H, int W, int c, int h,
+                                 int w, int sy, int sx, void* stream) {
+  LDM_CHECK_ARG(canvas && x_win, "ldm_window_gather: null pointer");
+  LDM_CHECK_ARG(DT_OK(x_dtype), "ldm_window_gather: bad x_dtype %d", x_dtype);
+  const int st = grid_check("ldm_window_gather", B, H, W, c, h, w, sy, sx);
+  if (st != LDM_OK) return st;
+  const Grid1 gy = grid1(H, h, sy), gx = grid1(W, w, sx);
+  const int64_t half = (int64_t)B * gy.n * gx.n * h * w * c;
+  // four-wide: the canvas is read and a float32 batch written in 16-byte accesses, a bf16 batch in 8-byte ones
+  const bool wide = c % 4 == 0 && al(canvas, 16) && al(x_win, x_dtype == LDM_BF16 ? 8 : 16);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 g(grid_for(wide ? half / 4 : half, 256, 1024));
+#define GATHER(TX, V) \
+  hipLaunchKernelGGL((window_gather_kernel<TX, V>), g, dim3(256), 0, s, canvas, (TX*)x_win, B, c, gy, gx)
+  if (x_dtype == LDM_BF16) {
+    if (wide) GATHER(bf16_t, 4); else GATHER(bf16_t, 1);
+  } else {
+    if (wide) GATHER(float, 4); else GATHER(float, 1);
+  }
+#undef GATHER
+  return ldm_launch_status("ldm_window_gather");
+}
+
+extern "C" int ldm_window_fold(const float* eps_win, float* eps_canvas, int halves, int B, int H, int W, int c, int h,
+                               int w, int sy, int sx, void* stream) {
+  LDM_CHECK_ARG(eps_win && eps_canvas, "ldm_window_fold: null pointer");
+  LDM_CHECK_ARG(halves == 1 || halves == 2, "ldm_window_fold: halves=%d must be 1 or 2", halves);
+  const int st = grid_check("ldm_window_fold", B, H, W, c, h, w, sy, sx);
+  if (st != LDM_OK) return st;
+  const Grid1 gy = grid1(H, h, sy), gx = grid1(W, w, sx);
+  const bool wide = c % 4 == 0 && al(eps_win, 16) && al(eps_canvas, 16);
+  const int64_t total = (int64_t)halves * B * H * W * c;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 g(grid_for(wide ? total / 4 : total, 256, 1024));
+  if (wide) hipLaunchKernelGGL(window_fold_kernel<4>, g, dim3(256), 0, s, eps_win, eps_canvas, halves * B, c, gy, gx);
+  else hipLaunchKernelGGL(window_fold_kernel<1>, g, dim3(256), 0, s, eps_win, eps_canvas, halves * B, c, gy, gx);
+  return ldm_launch_status("ldm_window_fold");
+}

@@ -37,6 +37,11 @@ guidance scale: a float32 device table read by the one update launch (ldm_cfg_sc
 into a captured graph.  A step whose scale is exactly 1 is unguided: its eps is the conditional one by definition,
 and the U-Net runs on the conditional rows alone against the resident context.  A loop replays one of two captured
 graphs per step.  eta must be 0 there; a float scale without an interval takes the path above unchanged.
+
+ddim_p_sample_loop_panorama samples a canvas wider than the U-Net's training size: every step
+crops the canvas into overlapping training-size windows (ldm_window_gather), runs the U-Net on the window rows,
+averages the windows' eps back onto the canvas (ldm_window_fold) and runs the configured solver's one update launch
+on the canvas.  The updates are affine in eps, so that equals averaging the windows' step outputs (MultiDiffusion).
 """
 from __future__ import annotations
 
@@ -46,6 +51,7 @@ import numpy as np
 import torch
 
 from . import ops
+from ._lib import LdmHipError
 from .autoencoder import AutoencoderKL, AutoencoderVQ
 
 
@@ -155,6 +161,34 @@ def latent_mask(pixel_mask, f):
   B, H, W = m.shape
   keep = (m != 0).reshape(B, H // f, f, W // f, f).all(axis=(2, 4))
   return keep.astype(np.float32)
+
+
+def window_origins(L, l, s):
+  """Origins of the windows of extent l at stride s covering an axis of extent L:
+  n = ceil((L - l) / s) + 1 windows, origin_i = min(i * s, L - l); the last one is clamped to the edge.  Needs
+  1 <= l <= L and 1 <= s <= l (no gaps); strictly increasing."""
+  L, l, s = int(L), int(l), int(s)
+  if not 1 <= l <= L:
+    raise ValueError(f"window extent {l} must lie in [1, {L}] (the canvas extent)")
+  if not 1 <= s <= l:
+    raise ValueError(f"window stride {s} must lie in [1, {l}] (the window extent): windows leave no gaps")
+  n = -((l - L) // s) + 1
+  return [min(i * s, L - l) for i in range(n)]
+
+
+def window_and_stride(window, stride=None):
+  """((h, w), (sy, sx)) of a panorama call: each argument one int (both axes) or a pair; `stride` None = half the
+  window, rounded down, at least 1."""
+  def pair(v, what):
+    if np.ndim(v) == 0:
+      v = (v, v)
+    if np.ndim(v) != 1 or len(v) != 2 or any(int(x) != x for x in v):
+      raise ValueError(f"{what} must be an int or a pair of ints, got {v!r}")
+    return tuple(int(x) for x in v)
+  h, w = pair(window, "window")
+  if stride is None:
+    stride = (max(h // 2, 1), max(w // 2, 1))
+  return (h, w), pair(stride, "stride")
 
 
 def guidance_table(steps, guidance_scale, guidance_interval=None):
@@ -511,6 +545,12 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     # selects the step's row of the temb table), so a loop starts from index = N and ends at 0.
     self._unet.forward(self._x2, steps=self._steps_dev, index=self._index_dev, out=self._eps, paired_rows=True,
                        **self._temb_kwargs(dec_index))
+    self._update(guidance_scale, clip_denoised, noise_table, dec_index, self._x2, pred_x0_out, masked, rng)
+
+  def _update(self, guidance_scale, clip_denoised, noise_table, dec_index, x_unet_out, pred_x0_out=None, masked=False,
+              rng=False):
+    """The one update launch of the configured solver on _eps / _xt (`x_unet_out`: where the next U-Net input goes,
+    None = nowhere)."""
     rng, multistep = bool(rng), self._sampler in MULTISTEP
     # (device noise: no tables; multistep: eta = 0, so no noise table either, and the loops never clip)
     assert noise_table is None or not (rng or multistep)
@@ -519,7 +559,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
               ("ddim", True): ops.cfg_ddim_update_rng,
               ("plms", False): ops.cfg_plms_update, ("plms", True): ops.cfg_plms_update_rng,
               ("deis", False): ops.cfg_ms_update, ("deis", True): ops.cfg_ms_update_rng}[self._sampler, rng]
-    kw = dict(coef=self._coef_dev, index=self._index_dev, guidance_scale=guidance_scale, x_unet_out=self._x2,
+    kw = dict(coef=self._coef_dev, index=self._index_dev, guidance_scale=guidance_scale, x_unet_out=x_unet_out,
               dec_index=dec_index and not self._pre_dec, pred_x0_out=pred_x0_out, **self._blend_kwargs(masked, rng))
     if multistep:
       kw.update(ring=self._ring, start=self._start)
@@ -902,6 +942,76 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     self._sample_loop(k, reset, lambda dec: self._step(guidance_scale, False, noise_table, dec_index=dec,
                                                         masked=masked, rng=rng), gkey, record)
     return self._finish(self._xt)
+
+  # ---- panorama ---------------------------------------------------------
+  def _alloc_windows(self, B, n_win, h, w, c):
+    """The window batch: the U-Net's input and output rows [uncond ; cond] x B x n_win, float32 (the U-Net's input
+    dtype).  A new address drops the captured graphs."""
+    key = (B, n_win, h, w, c)
+    if getattr(self, "_win_key", None) != key:
+      rows = 2 * B * n_win
+      self._x_win = torch.empty(rows, h, w, c, dtype=torch.float32, device=self.device)
+      self._eps_win = torch.empty(rows, h, w, c, dtype=torch.float32, device=self.device)
+      self._win_key = key
+      self._drop_graphs()
+
+  def _step_panorama(self, guidance_scale, noise_table, dec_index, window, stride, rng=False):
+    """gather(canvas) -> unet(window rows) -> fold(eps) -> the solver's update on the canvas.  The update writes no
+    U-Net input: the next step's gather reads the canvas."""
+    B, H, W, c = self._xt.shape
+    ops.window_gather(self._xt, self._x_win, window, stride)
+    self._unet.forward(self._x_win, steps=self._steps_dev, index=self._index_dev, out=self._eps_win, paired_rows=True,
+                       **self._temb_kwargs(dec_index))
+    ops.window_fold(self._eps_win, self._eps.view(2, B, H, W, c), window, stride)
+    self._update(guidance_scale, False, noise_table, dec_index, None, rng=rng)
+
+  def ddim_p_sample_loop_panorama(self, cond_model_inputs, shape, window, stride=None, guidance_scale=5., x_T=None,
+                                  noises=None, seed=0, first_sample_index=0, record=None, guidance_interval=None):
+    """MultiDiffusion (Bar-Tal et al. 2023) on the loop of ddim_p_sample_loop.  `shape` is the
+    canvas [B,H,W,c]; `window` = (h, w) the size the U-Net runs at; `stride` = (sy, sx), default half the window
+    (at least 1); one int means both axes.  Windows lie at window_origins() along each axis, the last one clamped to the edge.  Every step
+    evaluates the U-Net on the 2 * B * nW window rows and steps the canvas once with the mean eps of the windows
+    covering each cell.  x_T, noises ([N,B,H,W,c]), seed and record are the canvas's, as in ddim_p_sample_loop; every
+    sampler=, step table and noise source runs.  A window equal to the canvas is ddim_p_sample_loop bit for bit.
+    `guidance_scale` is one float: schedules (a sequence, `guidance_interval`) are not supported here."""
+    if np.ndim(guidance_scale) > 0 or guidance_interval is not None:
+      raise ValueError("the panorama loop takes one float guidance_scale: a sequence guidance_scale or a "
+                       "guidance_interval is not supported")
+    B, H, W, c = (int(s) for s in shape)
+    (h, w), (sy, sx) = window_and_stride(window, stride)
+    n_win = len(window_origins(H, h, sy)) * len(window_origins(W, w, sx))        # (ValueError: no such grid)
+    context = self._cond_stage_model(cond_model_inputs)
+    n = len(self._ddim_steps)
+    xt = self._x_T(x_T, seed, first_sample_index, B, H, W, c)
+    self._alloc_state(B, H, W, c)
+    self._alloc_windows(B, n_win, h, w, c)
+    # row (half, b, k) of the window batch attends to context[half * B + b]
+    context = torch.as_tensor(context).to(self.device)
+    if context.shape[0] != 2 * B:
+      raise ValueError(f"cond_model_inputs gives {context.shape[0]} context rows, the canvas batch needs {2 * B}")
+    self._set_context(torch.cat([context[:B].repeat_interleave(n_win, 0), context[B:].repeat_interleave(n_win, 0)]))
+    rng = self._draws_on_device(noises)
+    noise_table = None if rng else self._eta_noise_table(noises, seed, first_sample_index, B, H, W, c)
+
+    def reset():
+      # (the first gather reads the canvas: no [xt; xt] copies)
+      if self._noise_source == "device":
+        self._set_rng(seed, first_sample_index)
+      if xt is None:
+        ops.normal_fill(self._xt, self._rng, XT_STREAM)
+      else:
+        self._xt.copy_(xt)
+      self._index_dev.fill_(self._loop_start_index(n))
+      self._set_loop_start(n - 1)
+
+    gkey = ("panorama", (B, H, W, c), (h, w), (sy, sx), float(guidance_scale), noise_table is not None,
+            self._ctx_shape, False, self._noise_source, rng, self._step_spacing, self._sampler)
+    self._sample_loop(n, reset, lambda dec: self._step_panorama(guidance_scale, noise_table, dec, (h, w), (sy, sx),
+                                                                rng=rng), gkey, record)
+    try:
+      return self._finish(self._xt)
+    except LdmHipError as e:
+      raise ValueError(f"the decoder cannot decode a canvas of shape {[B, H, W, c]}: {e}") from e
 
   def ddim_p_sample_loop_progressive(self, cond_model_inputs, shape, guidance_scale=5.,
                                      record_freq=5, x_T=None, noises=None, seed=0,

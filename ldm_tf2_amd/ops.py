@@ -21,7 +21,7 @@ __all__ = [
     "bmm_nt", "conv3x3_small", "groupnorm", "layernorm", "softmax_rows", "attention",
     "time_embedding", "gemv", "cfg_ddim_update", "cfg_ddim_update_masked", "cfg_plms_update", "q_sample",
     "philox_u32", "normal_fill", "q_sample_rng", "cfg_ddim_update_rng", "cfg_plms_update_rng", "cfg_ms_update",
-    "cfg_ms_update_rng", "cfg_sched_update", "post_quant", "vq_nearest", "embedding",
+    "cfg_ms_update_rng", "cfg_sched_update", "window_gather", "window_fold", "post_quant", "vq_nearest", "embedding",
     "minmax_u8", "cast",
 ]
 
@@ -995,6 +995,40 @@ def cfg_sched_update(eps_all, xt, xt_out, coef, gtab, index, guided, ring=None, 
       *_blend_args(xt, coef, z0, mask, q_coef, q_noise, q_index_stride, table=rng is None), _stream()),
         "ldm_cfg_sched_update")
   return xt_out
+
+
+def _window_args(canvas, win, lead, window, stride, what):
+  """The shared checks of window_gather / window_fold -> (B, H, W, c, h, w, sy, sx).  canvas [B,H,W,c] (fold:
+  [halves,B,H,W,c], `lead` = halves), win = `lead` x [B,nW,h,w,c]; a window or stride outside the canvas is left to
+  the launcher (it reports it), every valid grid has the batch's size checked here."""
+  (h, w), (sy, sx) = (int(v) for v in window), (int(v) for v in stride)
+  B, H, W, c = (int(v) for v in canvas.shape[-4:])
+  assert canvas.is_contiguous() and win.is_contiguous(), what
+  if 1 <= h <= H and 1 <= w <= W and 1 <= sy <= h and 1 <= sx <= w:
+    n_win = (-((h - H) // sy) + 1) * (-((w - W) // sx) + 1)
+    assert win.numel() == lead * B * n_win * h * w * c, (what, tuple(win.shape), (lead, B, n_win, h, w, c))
+  return B, H, W, c, h, w, sy, sx
+
+
+def window_gather(canvas, x_win, window, stride):
+  """Panorama (include/ldm_hip.h): canvas [B,H,W,c] float32 -> x_win [2,B,nW,h,w,c] (float32 or
+  bfloat16), both halves the crops of the `window` = (h, w) grid at `stride` = (sy, sx), last window clamped."""
+  assert canvas.dim() == 4, tuple(canvas.shape)
+  dims = _window_args(canvas, x_win, 2, window, stride, "window_gather")
+  check(lib.ldm_window_gather(_ptr(_f32(canvas, "canvas")), _ptr(x_win), code(x_win.dtype), *dims, _stream()),
+        "ldm_window_gather")
+  return x_win
+
+
+def window_fold(eps_win, eps_canvas, window, stride):
+  """Panorama: eps_win [halves,B,nW,h,w,c] float32 -> eps_canvas [halves,B,H,W,c] float32, every canvas element the
+  float32 mean of the windows covering it (ascending window index, one correctly rounded division); halves 1 or 2."""
+  assert eps_canvas.dim() == 5, tuple(eps_canvas.shape)
+  halves = int(eps_canvas.shape[0])
+  dims = _window_args(eps_canvas, eps_win, halves, window, stride, "window_fold")
+  check(lib.ldm_window_fold(_ptr(_f32(eps_win, "eps_win")), _ptr(_f32(eps_canvas, "eps_canvas")), halves, *dims,
+                            _stream()), "ldm_window_fold")
+  return eps_canvas
 
 
 def post_quant(latents, scale_factor, kernel_io, bias, out):

@@ -37,6 +37,12 @@ Guidance schedule: `ldm_sampling.guidance_scale` may be a list of `ldm.num_ddim_
 the optional key `ldm_sampling.guidance_interval: [t_lo, t_hi]` (training timesteps, inclusive) guides only the steps
 inside it; steps whose scale is 1 evaluate the U-Net on the conditional rows alone (needs `ldm.eta` 0; DESIGN.md
 section 11).  Every loop above honours both.
+
+Panorama: optional `ldm_sampling` keys `window: [h, w]` and `window_stride: [sy, sx]` (default: half the window).  With
+`window`, `latent_shape` is a canvas larger than the U-Net's training size: every step runs the U-Net on overlapping
+`window`-sized crops of the canvas and averages their predictions where they overlap (MultiDiffusion; DESIGN.md
+section 12).  Every solver, step table and noise source runs; `init_image`, `mask`, `sample_save_progress`,
+`guidance_interval` and a list `guidance_scale` cannot be combined with it.  Without `window` nothing changes.
 """
 from __future__ import annotations
 
@@ -50,7 +56,7 @@ import yaml
 
 from . import ops
 from .autoencoder import AutoencoderKL, AutoencoderVQ
-from .model_runners import LatentDiffusionModelSampler, latent_mask
+from .model_runners import LatentDiffusionModelSampler, latent_mask, window_and_stride
 from .tokenizer import get_token_ids
 from .transformer import TransformerModel
 from .unet import UNet
@@ -132,10 +138,30 @@ def guidance_kwargs(config):
   return dict(guidance_interval=(iv[0], iv[1]))
 
 
+def panorama_kwargs(config, seed):
+  """`ldm_sampling.window: [h, w]` / `window_stride: [sy, sx]` (default: half the window) as the panorama loop's
+  keywords (the reference's YAML has no such keys).  The loop has no init image, mask, progress
+  frames or guidance schedule."""
+  samp = config["ldm_sampling"]
+  for key in ("init_image", "mask", "sample_save_progress", "guidance_interval"):
+    if samp.get(key) is not None and samp.get(key) is not False:
+      raise ValueError(f"ldm_sampling.window cannot be combined with ldm_sampling.{key}")
+  if np.ndim(samp["guidance_scale"]) > 0:
+    raise ValueError("ldm_sampling.window needs one float guidance_scale, not a list")
+  for key in ("window", "window_stride"):
+    v = samp.get(key)
+    if v is not None and (not isinstance(v, (list, tuple)) or len(v) != 2):
+      raise ValueError(f"ldm_sampling.{key} must be a pair of ints, got {v!r}")
+  window, stride = window_and_stride(samp["window"], samp.get("window_stride"))
+  return dict(window=window, stride=stride, seed=seed)
+
+
 def sampling_call(config, token_ids, seed):
   """(sampler method name, positional args, kwargs) of the call main() makes for `config`."""
   samp = config["ldm_sampling"]
   base = (token_ids, samp["latent_shape"], samp["guidance_scale"])
+  if samp.get("window") is not None:
+    return "ddim_p_sample_loop_panorama", base, panorama_kwargs(config, seed)
   if samp.get("mask") is not None and not samp.get("init_image"):
     raise ValueError("ldm_sampling.mask needs ldm_sampling.init_image")
   if samp.get("init_image"):
