@@ -35,22 +35,26 @@ LN_EPS = 1e-5       # unet.py:304-306
 
 
 class _Res:
-  """ResidualBlock weights (unet.py:368-380)."""
+  """ResidualBlock weights (unet.py:368-380).  The second convolution and the shortcut are kept in the one form
+  the block launches: `conv2_sc` (a block with a shortcut, `merge_shortcut`), else `conv2` and, where the block has
+  one, `shortcut`; the operands of the other form are None."""
 
-  def __init__(self, w, p, dtype, dev):
+  def __init__(self, w, p, dtype, dev, merge_shortcut=True):
     g = lambda n: w[p + "/" + n]
     self.cin, self.cout = g("conv2d_1/kernel").shape[2], g("conv2d_1/kernel").shape[3]
     self.gn1 = (L.vec(g("group_norm_1/gamma"), dev), L.vec(g("group_norm_1/beta"), dev))
     self.conv1 = (L.conv_kernel(g("conv2d_1/kernel"), dtype, dev), L.vec(g("conv2d_1/bias"), dev))
     self.temb_k, self.temb_b = g("dense/kernel"), g("dense/bias")   # gathered by the U-Net
     self.gn2 = (L.vec(g("group_norm_2/gamma"), dev), L.vec(g("group_norm_2/beta"), dev))
-    self.conv2 = (L.conv_kernel(g("conv2d_2/kernel"), dtype, dev), L.vec(g("conv2d_2/bias"), dev))
-    self.shortcut = self.conv2_sc = None
-    if (p + "/shortcut/kernel") in w:
-      self.shortcut = (L.dense_kernel(g("shortcut/kernel"), dtype, dev), L.vec(g("shortcut/bias"), dev))
+    self.conv2 = self.shortcut = self.conv2_sc = None
+    if (p + "/shortcut/kernel") in w and merge_shortcut:
       # the shortcut as extra K columns of the second convolution (ldm_gemm a2): [Cout, 9 Cout + Cin], bias sum
       self.conv2_sc = (L.conv_shortcut_kernel(g("conv2d_2/kernel"), g("shortcut/kernel"), dtype, dev),
                        L.vec(np.asarray(g("conv2d_2/bias"), dtype=np.float32) + np.asarray(g("shortcut/bias"), dtype=np.float32), dev))
+    else:
+      self.conv2 = (L.conv_kernel(g("conv2d_2/kernel"), dtype, dev), L.vec(g("conv2d_2/bias"), dev))
+      if (p + "/shortcut/kernel") in w:
+        self.shortcut = (L.dense_kernel(g("shortcut/kernel"), dtype, dev), L.vec(g("shortcut/bias"), dev))
     self.temb_off = 0
 
 
@@ -114,8 +118,7 @@ class _ST:
                          row_scale=None if qk_scale is None else torch.cat([qk_scale, torch.ones(hs)]),
                          bias_extra=None if qk_ones is None else torch.cat([qk_ones, v_ones])),
           qk1=L.ln_fold(qk_f, lnp[0][0], lnp[0][1], None, dtype, dev, row_scale=qk_scale, bias_extra=qk_ones),
-          v1=L.ln_fold(L.split_kernel(w[a1 + "/value/kernel"], sp, f32, cpu), lnp[0][0], lnp[0][1], None, dtype, dev,
-                       bias_extra=v_ones),
+          v1=L.ln_fold(v_f, lnp[0][0], lnp[0][1], None, dtype, dev, bias_extra=v_ones),
           q2=L.ln_fold(L.split_kernel(w[a2 + "/query/kernel"], sp, f32, cpu), lnp[1][0], lnp[1][1], None, dtype, dev,
                        row_scale=q_scale),
           geglu=L.ln_fold(gw, lnp[2][0], lnp[2][1], gb.numpy(), dtype, dev))
@@ -137,7 +140,9 @@ class UNet:
                num_heads=8, *, weights=None, dtype=torch.float32, device="cuda:0",
                context_dim=1280, init="keras", seed=2, fuse_layernorm=False, fuse_qkv=True,
                split_qkv=True, small_conv_out=False, fold_layernorm=True, fold_min_rows=2048,
-               defer_reduce=True, matrix_softmax=True, gn_single_launch=True, fused_ffn=True, ffn_min_rows=24576, fused_tail=True, fused_xattn=True, fused_block=True, lanes=1, lane_levels=None, shared_prefix=True, merge_qkv=True, merge_qkv_max_rows=1 << 30,
+               defer_reduce=True, matrix_softmax=True, gn_single_launch=True, fused_ffn=True,
+               ffn_min_rows=24576, fused_tail=True, fused_xattn=True, fused_block=True,
+               shared_prefix=True, merge_qkv=True, merge_qkv_max_rows=1 << 30,
                merge_shortcut=True, merge_ffproj=True, block_min_rows=12288):
     # fuse_layernorm: the transformer blocks' LayerNorms come out of the producing GEMM's epilogue
     # where its tile holds whole rows (C = 320).  Measured on MI355X at R=32: 11.02 vs 10.95 ms per
@@ -166,11 +171,6 @@ class UNet:
     self._ffn_min_rows = int(ffn_min_rows)        # ... from 192 panels of 128 rows on (3/4 of the CUs busy)
     self._gn_single = bool(gn_single_launch)      # False: partial-sums + apply launches everywhere (A/B)
     self._defer_reduce = bool(defer_reduce)   # split-K reduces fused into the consuming GroupNorm (A/B: False)
-    # lanes: the rows of one evaluation walked as `lanes` coarse, independent branches (no op of the U-Net
-    # crosses rows, unet.py:118-138): branch i takes rows [i R / lanes, (i+1) R / lanes) on its own stream with
-    # its own scratch and split-K workspace -- ONE fork after the timestep MLP, ONE join before the caller's
-    # next launch -- so one branch's latency-bound launches run beside the other's convolutions.  Each
-    # branch runs the launch plans of ITS row count.
     self._merge_ffproj = bool(merge_ffproj)       # FF-out + proj_out as one folded product on the per-layer path (bf16; A/B: False)
     self._merge_shortcut = bool(merge_shortcut)   # ResBlock shortcut inside its second convolution's K loop (A/B: False)
     self._merge_qkv = bool(merge_qkv)             # LayerNorm-folded q | k | V^T as one launch (A/B: False = two)
@@ -178,13 +178,7 @@ class UNet:
     # balanced at M = 32768: 6 + 3 n-tiles on 2 workgroups per panel; ranges may straddle n_split now)
     self._merge_qkv_max_rows = int(merge_qkv_max_rows)
     self._shared_prefix = bool(shared_prefix)     # forward(paired_rows=True): the CFG pair's common prefix once (A/B: False)
-    self._lanes = max(1, int(lanes))
-    # lane_levels = L: only the levels from L down (the downsample conv into level L .. the upsample conv out of it)
-    # are branched, the full-resolution levels run unbranched on all rows; None: the whole evaluation
-    self._lane_levels = None if lane_levels is None else int(lane_levels)
-    self._lane_state = {}
-    self._rows = None                     # a lane's slice of the rows (context K / V^T); None = all rows
-    self._ctx_sel = None                  # the context rows those rows attend to (forward(context_rows=) offsets them)
+    self._ctx_sel = None                  # the context rows an evaluation attends to (forward(context_rows=)); None = all
     self._pend = None
     self._model_channels = model_channels
     self._out_channels = out_channels
@@ -215,7 +209,7 @@ class UNet:
     res_all = []
 
     def mk_res(p):
-      r = _Res(w, p, dt, dev)
+      r = _Res(w, p, dt, dev, merge_shortcut=self._merge_shortcut)
       res_all.append(r)
       return r
 
@@ -253,7 +247,7 @@ class UNet:
     self.gn_out = (L.vec(w["groupnorm/gamma"], dev), L.vec(w["groupnorm/beta"], dev))
     self.conv_out = (L.vec(w["conv_out/kernel"], dev), L.vec(w["conv_out/bias"], dev))
     # bf16: the 320 -> 4 output conv as an implicit-GEMM launch too (N = 4 of a 64-column tile is
-    # wasted MFMA work, but 3 GFLOP on the matrix cores beat the 8-lanes-per-pixel FMA kernel 4x);
+    # wasted MFMA work, but 3 GFLOP on the matrix cores beat the 8-threads-per-pixel FMA kernel 4x);
     # small_conv_out=True: the scalar kernel (A/B)
     self.conv_out_mm = (L.conv_kernel(w["conv_out/kernel"], dt, dev)
                         if dt == torch.bfloat16 and not self._small_conv_out else None)
@@ -325,8 +319,7 @@ class UNet:
     t0 = B_.get("gn", tuple(x.shape), dt)
     self._gn(x, r.gn1, GN_EPS_RES, True, t0)
     res = x
-    merged = r.shortcut is not None and self._merge_shortcut
-    if r.shortcut is not None and not merged:   # before conv1: the slabs of conv1 must survive until GN2
+    if r.shortcut is not None:                  # before conv1: the slabs of conv1 must survive until GN2
       res = B_.get("sc", (R, h, w, r.cout), dt)
       ops.linear(x, r.shortcut[0], res, bias=r.shortcut[1])
     h1 = B_.get("h1", (R, h, w, r.cout), dt)
@@ -334,7 +327,7 @@ class UNet:
     t1 = B_.get("gn", (R, h, w, r.cout), dt)
     self._gn(h1, r.gn2, GN_EPS_RES, True, t1, store_x=False)      # h1 has no other reader (unet.py:388-390)
     # conv2's reduce is left to the next GroupNorm (the following block's first op) when that reads `out`
-    if merged:
+    if r.conv2_sc is not None:
       # unet.py:393-397: shortcut(x) + conv2(...) as ONE product -- the shortcut's channels are extra K columns of
       # the convolution (ldm_gemm a2): no launch and no [M, Cout] tensor of its own
       self._conv_deferred(t1, r.conv2_sc[0], out, bias=r.conv2_sc[1], x2=x)
@@ -379,16 +372,14 @@ class UNet:
     # LayerNorm folded into its consumer (bf16, launches with enough rows for the persistent kernel)
     fold = st.fold if (st.fold is not None and R * T >= self._fold_min_rows and T % 32 == 0) else None
     # self-attention (unet.py:309-310)
+    if fold is None and not fuse_ln:
+      ops.layernorm(ha, st.ln[0][0], st.ln[0][1], ln, LN_EPS)
     if fold is not None and self._merge_qkv and R * T <= self._merge_qkv_max_rows and hs % 128 == 0:
       # q | k | V^T: one pass of the persistent kernel over the LayerNorm'ed rows (gemm3_kernel EPI bit 7)
       ops.linear(ha, fold["qkv1"][0], qk, bias=fold["qkv1"][2], ln_fold=(fold["qkv1"][1], LN_EPS), out2=vt)
     elif fold is not None:
       ops.linear(ha, fold["qk1"][0], qk, bias=fold["qk1"][2], ln_fold=(fold["qk1"][1], LN_EPS))
       ops.linear_t(ha, fold["v1"][0], vt, bias=fold["v1"][2], ln_fold=(fold["v1"][1], LN_EPS))
-    elif not fuse_ln:
-      ops.layernorm(ha, st.ln[0][0], st.ln[0][1], ln, LN_EPS)
-    if fold is not None:
-      pass
     elif self._split_qkv and ops.linear_t_supported(ln, st.v1, vt):
       # bf16: q|k row-major and v TRANSPOSED (straight into the attention kernel's V^T layout) as two
       # launches that can both take the persistent kernel (ops.linear_t)
@@ -514,83 +505,81 @@ class UNet:
     else:
       assert not pre_decrement
       tall = self._temb(R, t_rows, steps, index, shared_t)
-    env = self._env(x, tall, out)
-    env["ctx_lo"] = None if context_rows is None else int(context_rows[0])
-    env["pair"] = bool(paired_rows and self._shared_prefix and R % 2 == 0 and self._lanes == 1
-                       and self.in_blocks[0][0] == "res" and self.in_blocks[0][2] is not None)
-    prog = env["prog"]
-    n = self._lanes if (self._lanes > 1 and R % self._lanes == 0) else 1
-    if n == 1:
-      self._segment(env, 0, len(prog), None)
-      return out
-    # coarse row branches over the step range [a, b): lane 0 on the caller's stream, the others on side streams of
-    # their own (ONE fork, ONE join); under graph capture the side streams join the capture through the event
-    # waits.  Steps outside the range run unbranched on all rows.
-    a, b = self._lane_range(env)
-    Rl = R // n
-    cur = torch.cuda.current_stream(self.device)
-    lanes = self._lane_views(n)
-    if a > 0:
-      self._segment(env, 0, a, None)
-    for i in range(1, n):
-      ln, side = lanes[i]
-      side.wait_stream(cur)
-      with torch.cuda.stream(side):
-        ln._segment(env, a, b, slice(i * Rl, (i + 1) * Rl))
-    lanes[0][0]._segment(env, a, b, slice(0, Rl))
-    for i in range(1, n):
-      cur.wait_stream(lanes[i][1])
-    if b < len(prog):
-      self._segment(env, b, len(prog), None)
-    return out
-
-  def _lane_range(self, env):
-    """Step range the row branches cover: the whole evaluation (`lane_levels` None) or the levels from
-    `lane_levels` down -- first step = the downsample conv into that level, last = the upsample conv out of it."""
-    prog = env["prog"]
-    if self._lane_levels is None:
-      return 0, len(prog)
-    lv = [st[-1] for st in prog]
-    inside = [i for i, l in enumerate(lv) if l >= self._lane_levels]
-    return (inside[0], inside[-1] + 1) if inside else (0, 0)
-
-  def _lane_views(self, n):
-    """Shallow views of this model, one per branch: the weights are shared, scratch buffers, split-K workspace and
-    the deferred-product slot are the view's own (built once per lane count, before any capture needs them)."""
-    views = self._lane_state.get(n)
-    if views is None:
-      import copy
-      views = []
-      for i in range(n):
-        v = copy.copy(self)
-        v.buf = L.Buffers(self.device)
-        v._ws = ops.new_workspace(self.device)
-        v._pend = None
-        v._lanes, v._lane_state = 1, {}
-        views.append((v, torch.cuda.Stream(self.device) if i else None))
-      self._lane_state[n] = views
-    return views
-
-  def _segment(self, env, a, b, rows):
-    """Steps [a, b) of the evaluation on the rows `rows` (None = all), with this view's scratch and workspace and
-    the launch plans measured for this row count (ops.plan_scope)."""
-    x = env["x"]
-    nr = x.shape[0] if rows is None else rows.stop - rows.start
-    self._rows = rows
-    # the context rows of this segment's rows: all of them, a branch's slice, or offset by forward(context_rows=)
-    lo = env.get("ctx_lo")
-    if lo is None:
-      self._ctx_sel = rows
-    else:
-      self._ctx_sel = slice(lo, lo + nr) if rows is None else slice(lo + rows.start, lo + rows.stop)
-    with ops.plan_scope(nr, x.shape[1], self.dtype), ops.workspace_scope(self._ws):
+    self._ctx_sel = None if context_rows is None else slice(lo, lo + R)
+    # a CFG pair: the launches in front of the first cross-attention once, on the first R/2 rows
+    pair = bool(paired_rows and self._shared_prefix and R % 2 == 0
+                and self.in_blocks[0][0] == "res" and self.in_blocks[0][2] is not None)
+    B_, dt = self.buf, self.dtype
+    half = R // 2
+    n_in, n_out = len(self.in_blocks), len(self.out_blocks)
+    # the skip / concat buffers: cats[j] = input of output block j = [previous output | skip n_in - j]
+    prev_ch = [self.mid[2].cout] + [b[0].cout for b in self.out_blocks[:-1]]
+    cats = []
+    for j in range(n_out):
+      i = n_in - j
+      lv = self.skip_lvl[i]
+      cats.append(B_.get(f"cat{j}", (R, h >> lv, w >> lv, prev_ch[j] + self.skip_ch[i]), dt))
+    final = B_.get("final", (R, h, w, self.out_blocks[-1][0].cout), dt)
+    skip = lambda i: cats[n_in - i][..., prev_ch[n_in - i]:]       # where skip tensor i lives
+    # this model's scratch and workspace, the launch plans measured for this row count
+    with ops.plan_scope(R, h, dt), ops.workspace_scope(self._ws):
       self._pend = None
-      self._gnp = self.buf.get("gn_partial", (nr * 128 * 32 * 2,), torch.float32)
+      self._gnp = B_.get("gn_partial", (R * 128 * 32 * 2,), torch.float32)
       try:
-        for st in env["prog"][a:b]:
-          self._exec(env, st, rows)
+        if pair:
+          # both halves of x are the same rows -- the convolution once, its output copied (the skip tensor is read
+          # with all rows by the last output block)
+          d0 = skip(0)
+          ops.conv3x3_small(x[:half], self.conv_in[0], self.conv_in[1], d0[:half])
+          ops.cast(d0[:half], d0[half:])
+        else:
+          ops.conv3x3_small(x, self.conv_in[0], self.conv_in[1], skip(0))
+        for i, blk in enumerate(self.in_blocks):
+          cur, dst = skip(i), skip(i + 1)
+          if blk[0] == "down":
+            self._conv_deferred(cur, blk[1], dst, bias=blk[2], stride=2)     # (flushes first: it reads cur)
+            continue
+          _, r, st = blk
+          if st is None:
+            self._res(r, cur, tall, dst)
+          elif i == 0 and pair:
+            # the pair's common prefix: ResBlock + the transformer block's head on the first R/2 rows, with the
+            # launch plans of THAT row count; the block's tail (from the first cross-attention on) on all rows
+            self._flush()
+            with ops.plan_scope(half, h, dt):
+              tmp, tmp_full = self._pair_buf("blk_r", (half,) + tuple(dst.shape[1:3]) + (r.cout,), dt, True)
+              self._res(r, cur[:half], tall if tall.shape[0] == 1 else tall[:half], tmp)
+              self._st(st, tmp, dst, pair=True, x_full=tmp_full)
+          else:
+            tmp = B_.get("blk_r", (R,) + tuple(dst.shape[1:3]) + (r.cout,), dt)
+            self._res(r, cur, tall, tmp)
+            self._st(st, tmp, dst)
+        cur = skip(n_in)
+        r1, stm, r2 = self.mid
+        shp = (R,) + tuple(cur.shape[1:3]) + (r1.cout,)
+        m1 = self._res(r1, cur, tall, B_.get("blk_r", shp, dt))
+        m2 = self._st(stm, m1, B_.get("blk_s", shp, dt))
+        self._res(r2, m2, tall, cats[0][..., :r2.cout])
+        for j, (r, st, up) in enumerate(self.out_blocks):
+          xin = cats[j]
+          shp = (R, xin.shape[1], xin.shape[2], r.cout)
+          dst = final if j + 1 == n_out else cats[j + 1][..., :r.cout]
+          # the block's last stage writes dst, the ones before it scratch
+          o = self._res(r, xin, tall, dst if st is None and up is None else B_.get("blk_r", shp, dt))
+          if st is not None:
+            o = self._st(st, o, dst if up is None else B_.get("blk_s", shp, dt))
+          if up is not None:
+            self._flush()                                           # it reads o
+            ops.conv3x3(o, up[0], dst, bias=up[1], upsample=True)   # unet.py:44-47
+        t0 = B_.get("gn", tuple(final.shape), dt)
+        self._gn(final, self.gn_out, GN_EPS_RES, True, t0)
+        if self.conv_out_mm is not None:
+          ops.conv3x3(t0, self.conv_out_mm, out, bias=self.conv_out[1])
+        else:
+          ops.conv3x3_small(t0, self.conv_out[0], self.conv_out[1], out)
       finally:
         self._flush()
+    return out
 
   def temb_table(self, steps):
     """[len(steps), sum of Cout] float32: the temb projections of every timestep in `steps` (int32, device) -- the
@@ -617,102 +606,6 @@ class UNet:
     tall = B_.get("temb_all" + tag, (rt, self.temb_total), f32)
     ops.gemv(temb, self.temb_all[0], self.temb_all[1], tall, act_in=ops.ACT_SILU)
     return tall
-
-  def _env(self, x, tall, out):
-    """The evaluation as a flat program over buffers every branch shares: the skip / concat buffers `cats`
-    (cat[j] = input of output block j = [previous output | skip n_in - j]), the final feature map, x, out.
-    A step is (kind, index, level); a branch executes a range of steps on its row slice of these buffers."""
-    R, h, w, _ = x.shape
-    B_, dt = self.buf, self.dtype
-    n_in = len(self.in_blocks)
-    prev_ch = [self.mid[2].cout] + [b[0].cout for b in self.out_blocks[:-1]]
-    cats = []
-    for j in range(len(self.out_blocks)):
-      i = n_in - j
-      lv = self.skip_lvl[i]
-      cats.append(B_.get(f"cat{j}", (R, h >> lv, w >> lv, prev_ch[j] + self.skip_ch[i]), dt))
-    final = B_.get("final", (R, h, w, self.out_blocks[-1][0].cout), dt)
-    prog = [("conv_in", 0, 0)]
-    for i in range(n_in):
-      prog.append(("in", i, self.skip_lvl[i + 1]))
-    top = max(self.skip_lvl)
-    prog.append(("mid", 0, top))
-    for j in range(len(self.out_blocks)):
-      prog.append(("out", j, self.skip_lvl[n_in - j]))
-    prog.append(("final", 0, 0))
-    return dict(x=x, tall=tall, out=out, cats=cats, final=final, prev_ch=prev_ch, prog=prog)
-
-  def _exec(self, env, step, rows):
-    kind, idx, _ = step
-    B_, dt = self.buf, self.dtype
-    sl = (lambda t: t) if rows is None else (lambda t: t[rows])
-    x, out, cats, prev_ch = sl(env["x"]), sl(env["out"]), env["cats"], env["prev_ch"]
-    tall = env["tall"] if env["tall"].shape[0] == 1 else sl(env["tall"])
-    R = x.shape[0]
-    n_in = len(self.in_blocks)
-    skip_dst = lambda i: sl(cats[n_in - i])[..., prev_ch[n_in - i]:]
-    if kind == "conv_in":
-      if env.get("pair") and rows is None:
-        # a CFG pair: both halves of x are the same rows -- the convolution once, its output copied (the skip
-        # tensor is read with all rows by the last output block)
-        half = R // 2
-        d0 = skip_dst(0)
-        ops.conv3x3_small(x[:half], self.conv_in[0], self.conv_in[1], d0[:half])
-        ops.cast(d0[:half], d0[half:])
-      else:
-        ops.conv3x3_small(x, self.conv_in[0], self.conv_in[1], skip_dst(0))
-    elif kind == "in":
-      cur, dst = skip_dst(idx), skip_dst(idx + 1)
-      blk = self.in_blocks[idx]
-      if blk[0] == "down":
-        self._conv_deferred(cur, blk[1], dst, bias=blk[2], stride=2)     # (flushes first: it reads cur)
-      else:
-        _, r, st = blk
-        if st is None:
-          self._res(r, cur, tall, dst)
-        elif idx == 0 and env.get("pair") and rows is None:
-          # the CFG pair's common prefix: ResBlock + the transformer block's head on the first R/2 rows, with the
-          # launch plans of THAT row count; the block's tail (from the first cross-attention on) on all rows
-          half = R // 2
-          self._flush()
-          with ops.plan_scope(half, x.shape[1], dt):
-            tmp, tmp_full = self._pair_buf("blk_r", (half,) + tuple(dst.shape[1:3]) + (r.cout,), dt, True)
-            self._res(r, cur[:half], tall if tall.shape[0] == 1 else tall[:half], tmp)
-            self._st(st, tmp, dst, pair=True, x_full=tmp_full)
-        else:
-          tmp = B_.get("blk_r", (R,) + tuple(dst.shape[1:3]) + (r.cout,), dt)
-          self._res(r, cur, tall, tmp)
-          self._st(st, tmp, dst)
-    elif kind == "mid":
-      cur = skip_dst(n_in)
-      r1, stm, r2 = self.mid
-      shp = (R,) + tuple(cur.shape[1:3]) + (r1.cout,)
-      m1 = self._res(r1, cur, tall, B_.get("blk_r", shp, dt))
-      m2 = self._st(stm, m1, B_.get("blk_s", shp, dt))
-      self._res(r2, m2, tall, sl(cats[0])[..., :r2.cout])
-    elif kind == "out":
-      j = idx
-      r, st, up = self.out_blocks[j]
-      xin = sl(cats[j])
-      hh, ww = xin.shape[1], xin.shape[2]
-      last = j + 1 == len(self.out_blocks)
-      dst = sl(env["final"]) if last else sl(cats[j + 1])[..., :r.cout]
-      stages = 1 + (st is not None) + (up is not None)
-      o = self._res(r, xin, tall, dst if stages == 1 else B_.get("blk_r", (R, hh, ww, r.cout), dt))
-      if st is not None:
-        stages_left = 1 if up is not None else 0
-        o = self._st(st, o, dst if stages_left == 0 else B_.get("blk_s", (R, hh, ww, r.cout), dt))
-      if up is not None:
-        self._flush()                                           # it reads o
-        ops.conv3x3(o, up[0], dst, bias=up[1], upsample=True)   # unet.py:44-47
-    else:
-      final = sl(env["final"])
-      t0 = B_.get("gn", tuple(final.shape), dt)
-      self._gn(final, self.gn_out, GN_EPS_RES, True, t0)
-      if self.conv_out_mm is not None:
-        ops.conv3x3(t0, self.conv_out_mm, out, bias=self.conv_out[1])
-      else:
-        ops.conv3x3_small(t0, self.conv_out[0], self.conv_out[1], out)
 
   def __call__(self, inputs, time, context=None, y=None, training=False):
     """unet.py:118 contract: inputs [R,h,w,4], time int [R], context [R,T,D]."""

@@ -1,9 +1,5 @@
 """Round-4 launch forms against the CPU oracle and against the forms they replace (all through the C ABI).
 
-  * coarse row branches (`UNet(lanes=2)`): one evaluation walked as two independent branches of R / 2 rows on
-    two streams (unet.py:118-138 has no cross-row op).  float32: every row bit-identical to the single-branch
-    evaluation of its half (same plan table = same summation order); against the oracle inside the U-Net gate;
-    eager == captured graph == second replay; per-row timesteps; the DDIM loop through the sampler.
   * launch-plan robustness: a table entry whose tile cannot run a launch (persistent tile, epilogue not
     instantiated / deferred split-K product) falls back to the cost model instead of raising or recursing.
 """
@@ -18,7 +14,7 @@ pytestmark = pytest.mark.gpu
 from ldm_tf2_amd import ops, weights as Wt  # noqa: E402
 from oracle import ldm_oracle as O  # noqa: E402
 
-from test_models_gpu import CTX_DIM, KL_CFG, LDM, LOOP_REL, TXT_CFG, UNET_CFG, check  # noqa: E402
+from test_models_gpu import CTX_DIM, KL_CFG, LDM, TXT_CFG, UNET_CFG, check  # noqa: E402
 
 DT = [torch.float32, torch.bfloat16]
 
@@ -26,92 +22,6 @@ DT = [torch.float32, torch.bfloat16]
 @pytest.fixture(scope="module")
 def unet_w():
   return Wt.init_weights(Wt.unet_manifest(context_dim=CTX_DIM, **UNET_CFG), seed=2, mode="random", scope="unet")
-
-
-def _inputs(R, hw=16):
-  g = np.random.default_rng(0)
-  x = g.standard_normal((R, hw, hw, 4)).astype(np.float32)
-  ctx = g.standard_normal((R, 77, CTX_DIM)).astype(np.float32)
-  return x, ctx
-
-
-@pytest.mark.parametrize("dtype", DT, ids=["f32", "bf16"])
-def test_lanes_match_single_branch_and_oracle(dev, dtype, unet_w):
-  from ldm_tf2_amd.unet import UNet
-  R = 8
-  x, ctx = _inputs(R)
-  t = np.array([981, 981, 21, 500, 1, 77, 500, 640], dtype=np.int32)
-  xd, cd, td = (torch.from_numpy(a).to(dev) for a in (x, ctx, t))
-  two = UNet(**UNET_CFG, context_dim=CTX_DIM, weights=unet_w, dtype=dtype, device=dev, lanes=2)
-  got = two(xd, td, cd)
-  torch.cuda.synchronize()
-  # the same rows, half by half, on a single-branch model: identical launches, identical bits
-  one = UNet(**UNET_CFG, context_dim=CTX_DIM, weights=unet_w, dtype=dtype, device=dev)
-  for h in range(2):
-    rows = slice(h * R // 2, (h + 1) * R // 2)
-    ref = one(xd[rows].contiguous(), td[rows].contiguous(), cd[rows].contiguous())
-    torch.cuda.synchronize()
-    assert torch.equal(got[rows], ref), f"lane {h} differs from the single-branch evaluation of its rows"
-  # ... and the oracle on all rows
-  with torch.no_grad():
-    want = O.unet_forward(x, t, ctx, unet_w)
-  check(got, want, dtype, "unet lanes=2 vs oracle")
-
-
-def test_lanes_graph_replay_is_eager(dev, unet_w):
-  from ldm_tf2_amd.unet import UNet
-  R = 4
-  x, ctx = _inputs(R)
-  xd, cd = torch.from_numpy(x).to(dev), torch.from_numpy(ctx).to(dev)
-  t = torch.full((R,), 500, dtype=torch.int32, device=dev)
-  u = UNet(**UNET_CFG, context_dim=CTX_DIM, weights=unet_w, dtype=torch.float32, device=dev, lanes=2)
-  u.set_context(cd)
-  out = torch.empty(R, 16, 16, 4, device=dev)
-  u.forward(xd, t_rows=t, out=out, shared_t=True)
-  torch.cuda.synchronize()
-  eager = out.clone()
-  g = torch.cuda.CUDAGraph()
-  with torch.cuda.graph(g):
-    u.forward(xd, t_rows=t, out=out, shared_t=True)
-  for i in range(2):
-    out.zero_()
-    g.replay()
-    torch.cuda.synchronize()
-    assert torch.equal(out, eager), f"replay {i} of the two-branch graph differs from the eager evaluation"
-
-
-@pytest.mark.parametrize("dtype", DT, ids=["f32", "bf16"])
-def test_lanes_ddim_loop(dev, dtype, unet_w):
-  """The sampler's loop with a two-branch U-Net (graph replay) == the single-branch loop bit for bit at
-  float32 (B = 2: each branch carries the unconditional resp. conditional rows; one plan table: none for
-  this tiny model), and inside the loop gate against the oracle."""
-  from ldm_tf2_amd.autoencoder import AutoencoderKL
-  from ldm_tf2_amd.model_runners import LatentDiffusionModelSampler
-  from ldm_tf2_amd.transformer import TransformerModel
-  from ldm_tf2_amd.unet import UNet
-  txt_w = Wt.init_weights(Wt.transformer_manifest(**TXT_CFG), seed=2, mode="random", scope="cond_stage_model")
-  kl_w = Wt.init_weights(Wt.decoder_manifest(**KL_CFG), seed=2, mode="random", scope="autoencoder")
-  B = 2
-  g = np.random.default_rng(3)
-  ids = np.concatenate([np.tile(np.array([[101, 102] + [0] * 75]), (B, 1)), g.integers(0, 1000, size=(B, 77))], 0).astype(np.int64)
-  x_T = g.standard_normal((B, 16, 16, 4)).astype(np.float32)
-  res = []
-  for lanes in (1, 2):
-    unet = UNet(**UNET_CFG, context_dim=CTX_DIM, weights=unet_w, dtype=dtype, device=dev, lanes=lanes)
-    txt = TransformerModel(**TXT_CFG, weights=txt_w, dtype=dtype, device=dev)
-    ae = AutoencoderKL(**KL_CFG, weights=kl_w, dtype=dtype, device=dev)
-    s = LatentDiffusionModelSampler(unet, ae, txt, verbose=False, **LDM)
-    img = s.ddim_p_sample_loop(ids, [B, 16, 16, 4], guidance_scale=5., x_T=x_T)
-    torch.cuda.synchronize()
-    res.append((img.float().cpu(), s._xt.clone().cpu()))
-  if dtype == torch.float32:
-    assert torch.equal(res[0][1], res[1][1]) and torch.equal(res[0][0], res[1][0])
-  rec = []
-  with torch.no_grad():
-    O.ddim_p_sample_loop(ids, x_T, dict(unet=unet_w, autoencoder=kl_w, cond_stage_model=txt_w), LDM, guidance_scale=5.,
-                         record=rec, num_heads=8)
-  xt = rec[-1]
-  check(res[1][1], xt, dtype, "x_0 of the two-branch loop vs oracle", gate=LOOP_REL[dtype])
 
 
 @pytest.mark.parametrize("dtype", DT, ids=["f32", "bf16"])
