@@ -73,6 +73,13 @@ int ldm_last_error(char* buf, int n);
  *   source pixel (oy*stride + kh - 1, ox*stride + kw - 1), zero outside; with
  *   upsample = 1 the source image is first nearest-2x upsampled
  *   (src[i][j] = img[i/2][j/2]; 2H and 2W must then stay below 32768, H and W otherwise).
+ *   upsample = 2 computes the same convolution over the upsampled image as four 2x2 "phase"
+ *   convolutions over the image itself: output pixel (2i + a, 2j + b) is
+ *     sum over dy, dx in {0,1}, ci of img[i - 1 + a + dy][j - 1 + b + dx][ci] * w[2a + b][n][(dy, dx, ci)],
+ *   w being [4][N][K = 4*Cin] with the 3x3 taps that fall on one image pixel summed beforehand
+ *   (layout.upsample_phase_kernel): 4/9 of the multiply-adds.  Stride 1; M = B*2H*2W as with
+ *   upsample = 1; bias / addend / residual and split-K as ever; no a2, out2, ln_out, GEGLU;
+ *   tiles 2, 9, 11 (bf16) and 1, 2 (f32).
  *   Cin must be a multiple of 128/sizeof(elem).
  *   Replaces: Conv2D 3x3 SAME (unet.py:22,40,71,375,378; autoencoder.py:32,35,
  *   148,275), pad(1,1)+stride-2 VALID (unet.py:26-27), ResizeNearestNeighbor+conv

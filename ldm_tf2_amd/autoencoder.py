@@ -123,10 +123,14 @@ class _Blocks:
 class _Decoder(_Blocks):
   """Decoder (autoencoder.py:252-298) + post_quant_conv (+ VQ codebook)."""
 
-  def __init__(self, weights, dtype, device, attention_resolutions):
+  def __init__(self, weights, dtype, device, attention_resolutions, phase_upsample=True):
     w, dev = weights, device
     self.dtype, self.device = dtype, dev
     self.attention_resolutions = tuple(attention_resolutions)
+    # upsample convolutions as four 2x2 phase convolutions over the image itself (ops.conv3x3_up2); only the
+    # weight form in use is built.  A/B: False = the nine-tap gather over the upsampled image
+    self._phase_upsample = bool(phase_upsample)
+    mk_up = L.upsample_phase_kernel if self._phase_upsample else L.conv_kernel
     self.codebook = L.vec(w["quantize/kernel"], dev) if "quantize/kernel" in w else None
     self.post_quant = (L.vec(w["post_quant_conv/kernel"], dev), L.vec(w["post_quant_conv/bias"], dev))
     self.conv_in = (L.vec(w["decoder/conv_in/kernel"], dev), L.vec(w["decoder/conv_in/bias"], dev))
@@ -138,7 +142,7 @@ class _Decoder(_Blocks):
     while any(k.startswith(f"decoder/up/{i}/") for k in w):
       p = f"decoder/up/{i}"
       if (p + "/conv/kernel") in w:
-        self.up.append(("up", L.conv_kernel(w[p + "/conv/kernel"], dtype, dev), L.vec(w[p + "/conv/bias"], dev)))
+        self.up.append(("up", mk_up(w[p + "/conv/kernel"], dtype, dev), L.vec(w[p + "/conv/bias"], dev)))
       else:
         a = _Attn(w, p + "/attention", dtype, dev) if (p + "/attention/group_norm/gamma") in w else None
         self.up.append(("res", _Res(w, p + "/residual", dtype, dev), a))
@@ -175,7 +179,7 @@ class _Decoder(_Blocks):
     for blk in self.up:
       if blk[0] == "up":
         h, w = 2 * h, 2 * w
-        ch = blk[1].shape[0]
+        ch = blk[1].shape[-2]             # Cout of [Cout, 9 Cin] and of the phase form's [4, Cout, 4 Cin]
       else:
         ch = max(blk[1].cin, blk[1].cout)
       best = max(best, h * w * ch)
@@ -211,8 +215,11 @@ class _Decoder(_Blocks):
     for blk in self.up:
       hh, ww = cur.shape[1], cur.shape[2]
       if blk[0] == "up":
-        dst = self._dst(cur, (B, 2 * hh, 2 * ww, blk[1].shape[0]))
-        cur = ops.conv3x3(cur, blk[1], dst, bias=blk[2], upsample=True)   # autoencoder.py:152-155
+        dst = self._dst(cur, (B, 2 * hh, 2 * ww, blk[1].shape[-2]))        # autoencoder.py:152-155
+        if self._phase_upsample:
+          cur = ops.conv3x3_up2(cur, blk[1], dst, bias=blk[2])
+        else:
+          cur = ops.conv3x3(cur, blk[1], dst, bias=blk[2], upsample=True)
       else:
         _, r, a = blk
         cur = self._res(r, cur, self._dst(cur, (B, hh, ww, r.cout)))
@@ -334,7 +341,7 @@ class _AutoencoderBase:
   _is_vq = False
 
   def _build(self, man_kwargs, weights, dtype, device, init, seed, attention_resolutions,
-             with_encoder=None, enc_kwargs=None):
+             with_encoder=None, enc_kwargs=None, phase_upsample=True):
     self.dtype, self.device = dtype, torch.device(device)
     self.manifest = decoder_manifest(**man_kwargs)
     if with_encoder is None:
@@ -346,7 +353,7 @@ class _AutoencoderBase:
     missing = [k for k in self.manifest if k not in weights]
     if missing:
       raise KeyError(f"autoencoder weights missing {len(missing)} tensors, e.g. {missing[:3]}")
-    self._decoder = _Decoder(weights, dtype, self.device, attention_resolutions)
+    self._decoder = _Decoder(weights, dtype, self.device, attention_resolutions, phase_upsample=phase_upsample)
     self._encoder = _Encoder(weights, dtype, self.device, attention_resolutions) if with_encoder else None
 
   def _encode(self, inputs, per_sample=False):
@@ -364,7 +371,7 @@ class AutoencoderKL(_AutoencoderBase):
   def __init__(self, latent_channels=4, channels=128, num_blocks=2, attention_resolutions=(),
                dropout_rate=0., multipliers=(1, 2, 4, 4), resample_with_conv=True, *,
                weights=None, dtype=torch.float32, device="cuda:0", init="keras", seed=2,
-               with_encoder=None, image_size=256):
+               with_encoder=None, image_size=256, phase_upsample=True):
     if not resample_with_conv:
       raise NotImplementedError("resample_with_conv=False is not on the sampling path")
     self._latent_channels, self._channels, self._num_blocks = latent_channels, channels, num_blocks
@@ -374,7 +381,7 @@ class AutoencoderKL(_AutoencoderBase):
                 weights, dtype, device, init, seed, (), with_encoder,
                 dict(latent_channels=latent_channels, channels=channels, num_blocks=num_blocks,
                      multipliers=self._multipliers, attention_resolutions=(), image_size=image_size,
-                     double_z=True))
+                     double_z=True), phase_upsample=phase_upsample)
 
   def encode(self, inputs, training=False, per_sample=False):
     """autoencoder.py:353-359: images [B,H,W,3] -> DiagonalGaussian posterior.  `per_sample`: one encoder pass

@@ -32,6 +32,10 @@
 //   * stride-1 convolutions at the 32x32 / 16x16 levels can run with a HALO-STAGED A operand (tiles
 //     15 / 16, gemm_kernel.h MODE 3): the (lines + 2) x (W + 2) input pixels of a 64-channel chunk are
 //     staged once and serve all nine taps; only the weight tiles go through the stage ring.
+//   * the 3x3 convolution over the nearest-2x upsampled image also runs as four 2x2 "phase" convolutions over
+//     the image itself (upsample = 2, gemm_kernel.h MODE 4): output pixel (2i + a, 2j + b) only sees a 2x2
+//     neighbourhood of the image, with weights summed beforehand (layout.upsample_phase_kernel) -- 16 instead
+//     of 36 multiply-adds per pixel, channel pair and output phase.
 //   * small-M layers (4x4 / 8x8 feature maps) stream their weights with split-K
 //     over all CUs; partial sums go to an f32 workspace and a second kernel
 //     reduces + applies the epilogue.
@@ -180,8 +184,16 @@ bool halo_ring_ok(const ldm_gemm_params* p) {
          p->OH == p->H && p->OW == p->W;
 }
 
+// the tiles instantiated for the phase form (upsample = 2): gemm_launch.h launch_phase
+bool phase_tile_ok(int c, int esize) { return c == 2 || (esize == 2 ? (c == 9 || c == 11) : c == 1); }
+// M-tiles of a launch: the phase form tiles the rows of each of its four phases (M / 4) separately
+inline int m_tiles(const ldm_gemm_params* p, int bm) {
+  return p->conv && p->upsample == 2 ? 4 * ((p->M / 4 + bm - 1) / bm) : (p->M + bm - 1) / bm;
+}
+
 template <typename T>
 void launch_mode(int cfg, const GemmArgs& a, dim3 grid, hipStream_t s) {
+  if (a.conv && a.upsample == 2) { launch_phase<T>(cfg, a, grid, s); return; }
   if (cfg == 15 || cfg == 16) {
     if constexpr (sizeof(T) == 2) launch_cfg<T, 3>(cfg, a, grid, s);
     return;
@@ -222,12 +234,13 @@ void choose(const ldm_gemm_params* p, int esize, int* cfg_out, int* split_out) {
     if ((c == 1 || c == 7) && esize == 2 && p->tile != c) continue;   // bf16: their ping-ponged twins 11 / 9 are ~20 % faster
     if (c == 6 && esize == 2 && p->tile != 6) continue;   // bf16: tile 10 (same 128x160 tile, 64x80 wave tiles) is 10-14 % faster
     if (kBf16Only[c] && esize != 2) continue;
+    if (p->conv && p->upsample == 2 && !phase_tile_ok(c, esize)) continue;   // phase form: its own few tiles
     if (p->a2 && (is_persistent(c) || is_halo_ring(c)) && p->tile != c) continue;   // second A operand: implicit-GEMM tiles only
     if (kTiles[c].bn % 160 == 0 && p->tile != c && (p->N % kTiles[c].bn != 0 || no160)) continue;   // 160/320-column tiles: N = 160*k layers
     if (p->out2 && p->n_split % kTiles[c].bn != 0) continue;                        // every tile on one side of n_split
     if (geglu && c > 2 && c != 5 && c != 11 && c != 12 && c != 14 && c != 19) continue;
     const TileCfg t = kTiles[c];
-    const double tiles = (double)cdiv(p->M, t.bm) * cdiv(p->N, t.bn) * p->batch;
+    const double tiles = (double)m_tiles(p, t.bm) * cdiv(p->N, t.bn) * p->batch;
     for (int split : kSplits) {
       if (p->split_k > 0 && split != p->split_k) continue;
       if (is_persistent(c) && split > 1) continue;   // the persistent kernel does not split K
@@ -242,7 +255,7 @@ void choose(const ldm_gemm_params* p, int esize, int* cfg_out, int* split_out) {
       // calibration (tools/splitk_sweep.py): when the 256x128 tiling cannot fill the chip once
       // (small-M convolutions: 4x4 / 8x8 / 16x16 maps), two co-resident 128x128 workgroups per
       // CU measure 5-14 % faster than one 256x128 at the same split
-      if (!no_t2pref && c == 2 && (double)cdiv(p->M, 256) * cdiv(p->N, 128) * p->batch < 256.0) us *= 0.9;
+      if (!no_t2pref && c == 2 && (double)m_tiles(p, 256) * cdiv(p->N, 128) * p->batch < 256.0) us *= 0.9;
       if (split > 1) us += 3.0 + (double)p->M * p->N * 4.0 * (split + 1) / 3.0e6;   // bytes / (3 TB/s) in us
       if (us < best) { best = us; best_cfg = c; best_split = split; }
     }
@@ -287,7 +300,7 @@ void build_args(const ldm_gemm_params* p, int cfg, int split, int kps, GemmArgs*
   int64_t a_bytes;
   if (p->conv) a_bytes = (((int64_t)p->B * p->H * p->W - 1) * p->lda + p->Cin) * esize;
   else a_bytes = (((int64_t)p->M - 1) * p->lda + (p->K - (p->a2 ? p->Cin2 : 0))) * esize;
-  const int64_t w_bytes = (int64_t)p->N * p->K * esize;
+  const int64_t w_bytes = (int64_t)p->N * p->K * esize;   // (phase form: of ONE phase's [N][K] block)
   GemmArgs a;
   memset(&a, 0, sizeof(a));
   a.a = (const char*)p->a; a.w = (const char*)p->w; a.bias = p->bias; a.addend = p->addend;
@@ -320,8 +333,11 @@ void build_args(const ldm_gemm_params* p, int cfg, int split, int kps, GemmArgs*
   a.split_k = split;
   a.ktiles_per_split = kps;
   const TileCfg t = kTiles[cfg];
-  a.tiles_m = cdiv(p->M, t.bm);
+  a.tiles_m = m_tiles(p, t.bm);
   a.tiles_n = cdiv(p->N, t.bn);
+#ifdef LDM_TOOLS_BUILD
+  { static const bool adj = getenv("LDM_UP2_PHASE_ADJACENT") != nullptr; a.phase_adjacent = adj; }   // tile-order A/B
+#endif
   *out = a;
 }
 
@@ -392,6 +408,15 @@ extern "C" int ldm_gemm(const ldm_gemm_params* p, void* stream) {
   if (p->conv) {
     LDM_CHECK_ARG(p->Cin > 0 && p->Cin % bke == 0, "ldm_gemm(conv): Cin=%d must be a multiple of %d",
                   p->Cin, bke);
+    if (p->upsample == 2) {
+      // phase form: four 2x2 convolutions over the image, weights [4][N][4*Cin] (layout.upsample_phase_kernel)
+      LDM_CHECK_ARG(p->K == 4 * p->Cin, "ldm_gemm(conv): the phase form (upsample = 2) needs K == 4*Cin (K=%d Cin=%d)", p->K, p->Cin);
+      LDM_CHECK_ARG(p->stride == 1 && !p->no_lead_pad, "ldm_gemm(conv): the phase form (upsample = 2) needs stride 1 (stride=%d)", p->stride);
+      LDM_CHECK_ARG(!p->a2 && !p->out2 && !p->ln_out && !p->ln_cs && p->act != LDM_ACT_GEGLU && p->ldc_n == 1,
+                    "ldm_gemm(conv): the phase form (upsample = 2) takes no second operand (a2), out2, ln_out, ln_cs or GEGLU "
+                    "and needs a row-major output");
+      LDM_CHECK_ARG(4ll * p->N * p->K * esize < (1ll << 31), "ldm_gemm(conv): the phase form's weights must be < 2 GiB");
+    } else
     LDM_CHECK_ARG(p->K == 9 * p->Cin + (p->a2 ? p->Cin2 : 0), "ldm_gemm(conv): K must be 9*Cin (+ Cin2 with a second operand)");
     if (p->a2) {
       LDM_CHECK_ARG(p->stride == 1 && !p->upsample && !p->no_lead_pad && p->OH == p->H && p->OW == p->W,
@@ -401,6 +426,7 @@ extern "C" int ldm_gemm(const ldm_gemm_params* p, void* stream) {
       LDM_CHECK_ARG((((int64_t)p->M - 1) * p->lda2 + p->Cin2) * esize < (1ll << 31), "ldm_gemm(conv): a2 extent must be < 2 GiB");
     }
     LDM_CHECK_ARG(p->stride == 1 || p->stride == 2, "ldm_gemm(conv): stride must be 1 or 2");
+    LDM_CHECK_ARG(p->upsample >= 0 && p->upsample <= 2, "ldm_gemm(conv): upsample must be 0, 1 or 2 (the phase form)");
     LDM_CHECK_ARG(p->B > 0 && p->H > 0 && p->W > 0 && p->OH > 0 && p->OW > 0, "ldm_gemm(conv): dims");
     LDM_CHECK_ARG(p->H < 32768 && p->W < 32768, "ldm_gemm(conv): H/W too large");
     LDM_CHECK_ARG(!(p->upsample && p->stride != 1), "ldm_gemm(conv): upsample needs stride 1");
@@ -461,6 +487,8 @@ extern "C" int ldm_gemm(const ldm_gemm_params* p, void* stream) {
   }
   if (p->act == LDM_ACT_GEGLU) LDM_CHECK_ARG(cfg <= 2 || cfg == 5 || cfg == 11 || cfg == 12 || cfg == 14 || cfg == 19, "ldm_gemm: GEGLU needs a tile whose width is a multiple of 64 (1, 2, 5, 11, 12)");
   LDM_CHECK_ARG(!kBf16Only[cfg] || esize == 2, "ldm_gemm: tile %d is bf16 only", cfg);
+  if (p->conv && p->upsample == 2)
+    LDM_CHECK_ARG(phase_tile_ok(cfg, esize), "ldm_gemm: tile %d has no phase form (upsample = 2): tiles 2, 9, 11 (bf16) / 1, 2 (f32)", cfg);
   LDM_CHECK_ARG(!p->a2 || (!is_persistent(cfg) && !is_halo_ring(cfg) && cfg < kNumTiles),
                 "ldm_gemm: tile %d cannot take a second A operand (a2): implicit-GEMM tiles 1-12, 17-19 only", cfg);
   if (is_halo_ring(cfg))

@@ -41,6 +41,7 @@ struct GemmArgs {
   int64_t lda2;              // output pixel) for the K-tiles kt >= kt9 (= K-tiles of the first; = ktiles when none)
   uint32_t a2_bytes;
   int kt9;
+  int phase_adjacent;        // MODE 4: tile order (0 = phase-major, 1 = the four phases of an M-tile adjacent)
 };
 
 constexpr int kLnTile = 8;   // the tile whose BN (320) holds a whole row of the N = 320 layers
@@ -105,6 +106,13 @@ __device__ __forceinline__ float apply_act(int act, float v) {
 //           16x16x32 fragment reads conflict-free at every shift) instead of one 32-piece A tile per tap (288 per
 //           chunk).  The patch of chunk c+1 lands while chunk c's nine taps are multiplied; only the
 //           weight tiles run through the 3-stage ring.
+//       4 = PHASE FORM of MODE 2: the 3x3 convolution over the nearest-2x upsampled image as four 2x2 convolutions
+//           over the image itself.  Output pixel (2i + a, 2j + b) reads the pixels (i - 1 + a + dy, j - 1 + b + dx),
+//           dy, dx in {0, 1}, with the phase's pre-summed weights (layout.upsample_phase_kernel: [4][N][4 Cin],
+//           phase = 2a + b).  It is MODE 1's gather with four taps (kt = chunk*4 + tap) and plain scalar tap
+//           offsets; the phase is one more tile coordinate, M-tiles count rows of ONE phase (M / 4 of them) and
+//           a row mp = (img, i, j) of the phase becomes output row (img, 2i + a, 2j + b) wherever a row index
+//           turns into an address (epilogue stores, split-K slabs).
 // MF:   0 = v_mfma_f32_32x32x16 (wave tile = TM x TN blocks of 32x32)
 //       1 = v_mfma_f32_16x16x32_bf16 (bf16 only; wave tile = blocks of 16x16, e.g. 64 x 80: the
 //           N = 160*k layers get a 2.2x larger wave tile per LDS byte read than 32 x 160)
@@ -179,7 +187,17 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
   }
   const int tile_id = bid % ntile;
   const int zz = bid / ntile;  // split index (split_k > 1) or batch index
-  const int tile_m = tile_id / p.tiles_n, tile_n = tile_id % p.tiles_n;
+  int tile_m = tile_id / p.tiles_n;
+  const int tile_n = tile_id % p.tiles_n;
+  [[maybe_unused]] int pa = 0, pb = 0;               // MODE 4: the phase (a, b) of this tile
+  if constexpr (MODE == 4) {
+    const int tpp = p.tiles_m >> 2;                  // M-tiles per phase
+    int phase;
+    if (p.phase_adjacent) { phase = tile_m & 3; tile_m >>= 2; }
+    else { phase = tile_m / tpp; tile_m -= phase * tpp; }
+    pa = phase >> 1; pb = phase & 1;
+  }
+  const int Mrows = MODE == 4 ? p.M >> 2 : p.M;      // rows the M-tiles count
   const int split = p.split_k > 1 ? zz : 0;
   const int bz = p.split_k > 1 ? 0 : zz;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
@@ -191,7 +209,8 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
   const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<char*>(p.a) + (int64_t)bz * p.stride_a * ES, 0, p.a_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<char*>(p.w) + (int64_t)bz * p.stride_w * ES, 0, p.w_bytes, 0x00020000);
+      const_cast<char*>(p.w) + (int64_t)bz * p.stride_w * ES + (MODE == 4 ? (int64_t)(pa * 2 + pb) * p.w_bytes : 0), 0,
+      p.w_bytes, 0x00020000);                          // (MODE 4: w_bytes = one phase's [N][K] block)
 
   // ---- per-lane staging geometry ---------------------------------------------
   // LDS-DMA instruction i of this wave fills rows g*8 .. g*8+7 (g = i*NW + wave) of the
@@ -209,8 +228,21 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
     const int m = m0 + row;
     a_base[i] = MODE == 0 ? (int)kOOB : 0; a_mask[i] = 0; a_aux[i] = 0;
     if constexpr (MODE <= 1) a2_base[i] = m < p.M ? (int)((int64_t)m * p.lda2 * ES) + ck * 16 : (int)kOOB;
-    if (m < p.M) {
-      if constexpr (MODE != 0) {
+    if (m < Mrows) {
+      if constexpr (MODE == 4) {
+        const int hw = p.H * p.W;
+        const int b = m / hw, rem = m - b * hw;
+        const int i0 = rem / p.W, j0 = rem - i0 * p.W;
+        const int iy0 = i0 - 1 + pa, ix0 = j0 - 1 + pb;
+        int mask = 0;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const int iy = iy0 + t / 2, ix = ix0 + t % 2;
+          if ((unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W) mask |= 1 << t;
+        }
+        a_mask[i] = mask;
+        a_base[i] = (int)(((int64_t)(b * p.H + iy0) * p.W + ix0) * p.lda * ES) + ck * 16;
+      } else if constexpr (MODE != 0) {
         const int ohw = p.OH * p.OW;
         const int b = m / ohw, rem = m - b * ohw;
         const int oy = rem / p.OW, ox = rem - oy * p.OW;
@@ -269,11 +301,12 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
       // of one 128-byte channel slice re-read the same pixels on consecutive K-tiles
       // (L1/L2 hits).  Only the summation order changes; the weight matrix keeps its
       // (tap, ci) layout.
-      const int cc = kt / 9;
-      const int tap = kt - cc * 9;
+      constexpr int NTAP = MODE == 4 ? 4 : 9, TW = MODE == 4 ? 2 : 3;   // (MODE 4: 2x2 taps, kt = chunk*4 + tap)
+      const int cc = kt / NTAP;
+      const int tap = kt - cc * NTAP;
       const int cib = cc * 128;                      // channel byte offset
       kb = tap * p.Cin * ES + cib;
-      const int kh = tap / 3, kw = tap - kh * 3;
+      const int kh = tap / TW, kw = tap - kh * TW;
       if constexpr (MODE == 2) {
 #pragma unroll
         for (int i = 0; i < LA; ++i) {
@@ -580,6 +613,17 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
   auto rowoff = [](int r) { return MF ? r : (r & 3) + 8 * (r >> 2); };
   const int mb = m0 + wm * WTM + 4 * lh;
   const int nb = n0 + wn * WTN + lr;
+  // row index -> output row: MODE 4 interleaves the phase's rows into the upsampled image
+  auto orow = [&](int m) __attribute__((always_inline)) -> int {
+    if constexpr (MODE == 4) {
+      const int hw = p.H * p.W;
+      const int b = m / hw, rem = m - b * hw;
+      const int i0 = rem / p.W, j0 = rem - i0 * p.W;
+      return (b * p.OH + 2 * i0 + pa) * p.OW + 2 * j0 + pb;
+    } else {
+      return m;
+    }
+  };
   if (p.out2 && n0 >= p.n_split) {
     // this tile lies in the transposed part: 4 consecutive rows of one sample are contiguous
     // in out2 (rows2 % 4 == 0, so a 4-row group never straddles two samples)
@@ -620,7 +664,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
           const int m = mb + i * MB + rowoff(r);
-          if (m < p.M) ws[(int64_t)m * p.N + n] = acc[i][j][r];
+          if (m < Mrows) ws[(int64_t)orow(m) * p.N + n] = acc[i][j][r];
         }
       }
     return;
@@ -653,7 +697,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
     // (2) row-wise pieces of 8 output columns per thread
     for (int c = tid; c < npieces; c += NT) {
       const int row = c / pcols, pc = c - row * pcols;
-      const int m = m0 + ep * EROWS + row;
+      int m = m0 + ep * EROWS + row;
       int ncol, lcol;                             // first output column, first LDS column (value)
       if (geglu) {
         const int oc = pc * 8;                    // within the tile's BN/2 output columns
@@ -663,7 +707,8 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
         lcol = pc * 8;
         ncol = n0 + lcol;
       }
-      if (m >= p.M || ncol >= nout) continue;
+      if (m >= Mrows || ncol >= nout) continue;
+      m = orow(m);
       float v[8];
       {
         const f32x4 x0 = *(const f32x4*)(sC + row * BN + lcol);
@@ -809,8 +854,9 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
         if (n >= p.N) continue;
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
-          const int m = mb + i * MB + rowoff(r);
-          if (m >= p.M) continue;
+          int m = mb + i * MB + rowoff(r);
+          if (m >= Mrows) continue;
+          m = orow(m);
           epi_store(p, bz, m, n, apply_act(p.act, epi_pre(p, m, n, acc[i][j][r])));
         }
       }
@@ -853,5 +899,8 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
 // host-side launcher of one (element type, MODE) pair; defined in gemm_inst_*.hip
 template <typename T, int MODE>
 void launch_cfg(int cfg, const GemmArgs& a, dim3 grid, hipStream_t s);
+// launcher of the MODE 4 tiles (the phase form of the upsample convolution); defined in gemm_inst_up2.hip
+template <typename T>
+void launch_phase(int cfg, const GemmArgs& a, dim3 grid, hipStream_t s);
 
 }  // namespace ldm_gemm_detail

@@ -37,4 +37,19 @@ void launch_cfg(int cfg, const GemmArgs& a, dim3 grid, hipStream_t s) {
   }
 }
 
+// MODE 4 (the upsample convolution as four 2x2 phase convolutions): only the tiles the workload runs --
+// 1 (f32 256x128), 2 (128x128, the small-M launches, split-K), 9 / 11 (bf16 ping-pong 256x160 / 256x128).
+// phase_tile_ok in gemm.hip names the same set.
+template <typename T>
+void launch_phase(int cfg, const GemmArgs& a, dim3 grid, hipStream_t s) {
+  if constexpr (sizeof(T) == 2) {
+    if (cfg == 9) hipLaunchKernelGGL((gemm_kernel<T, 256, 160, 4, 2, 4, 1, 1>), grid, dim3(512), 0, s, a);
+    else if (cfg == 11) hipLaunchKernelGGL((gemm_kernel<T, 256, 128, 4, 2, 4, 1, 1>), grid, dim3(512), 0, s, a);
+    else hipLaunchKernelGGL((gemm_kernel<T, 128, 128, 2, 2, 4>), grid, dim3(256), 0, s, a);
+  } else {
+    if (cfg == 1) hipLaunchKernelGGL((gemm_kernel<T, 256, 128, 4, 2, 4>), grid, dim3(512), 0, s, a);
+    else hipLaunchKernelGGL((gemm_kernel<T, 128, 128, 2, 2, 4>), grid, dim3(256), 0, s, a);
+  }
+}
+
 }  // namespace ldm_gemm_detail

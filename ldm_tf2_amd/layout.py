@@ -39,6 +39,29 @@ def conv_kernel(k_hwio, dtype, device):
   return _dev(k.permute(3, 0, 1, 2).reshape(cout, -1), dtype, device)
 
 
+def upsample_phase_kernel(k_hwio, dtype, device):
+  """[4][Cout][4*Cin]: a 3x3 kernel applied to the nearest-2x upsampled image, as the four 2x2 kernels that act on the
+  image itself (ldm_gemm's upsample = 2, ops.conv3x3_up2).  Output pixel (2i + a, 2j + b) reads the image rows
+  i - 1 + a + dy, dy in {0, 1}; the 3x3 rows that land on one image row are summed:
+      a = 0:  dy 0 <- kh 0,      dy 1 <- kh 1 + kh 2
+      a = 1:  dy 0 <- kh 0 + 1,  dy 1 <- kh 2
+  and the same for the columns with b, dx.  Phase p = 2a + b; within a phase the K order is tap (dy, dx) outer, ci
+  inner (conv_kernel's OHWI convention).  Summed in float64 from the unrounded kernel, rounded once to `dtype`."""
+  k = torch.from_numpy(np.ascontiguousarray(k_hwio)).to(torch.float64)     # [3, 3, Cin, Cout]
+  assert k.shape[0] == 3 and k.shape[1] == 3
+  cin, cout = k.shape[2], k.shape[3]
+  groups = (((0,), (1, 2)), ((0, 1), (2,)))          # [a or b][dy or dx] -> 3x3 rows / columns
+  out = torch.empty(4, cout, 4 * cin, dtype=torch.float64)
+  for a in range(2):
+    for b in range(2):
+      for dy in range(2):
+        for dx in range(2):
+          s = sum(k[kh, kw] for kh in groups[a][dy] for kw in groups[b][dx])     # [Cin, Cout]
+          t = dy * 2 + dx
+          out[2 * a + b, :, t * cin:(t + 1) * cin] = s.t()
+  return _dev(out, dtype, device)
+
+
 def conv_shortcut_kernel(k_hwio, k_io, dtype, device):
   """[Cout, 9*Cin + Cin2]: the 3x3 kernel's OHWI rows followed by the 1x1 shortcut's [out, in] rows -- ldm_gemm's
   K order with a second A operand (conv3x3(..., x2=...): the ResBlock shortcut inside its second convolution)."""

@@ -559,6 +559,32 @@ def conv3x3(x, wt, out, bias=None, stride=1, upsample=False, addend=None, residu
   return out
 
 
+def _up2_params(x, wt4, out, bias, tile, split_k):
+  B, H, W, Cin = x.shape
+  assert wt4.dim() == 3 and wt4.shape[0] == 4 and wt4.is_contiguous() and wt4.dtype == x.dtype
+  Cout = wt4.shape[1]
+  assert tuple(out.shape) == (B, 2 * H, 2 * W, Cout), (tuple(out.shape), (B, 2 * H, 2 * W, Cout))
+  p = GemmParams()
+  p.a, p.w, p.out = _ptr(x), _ptr(wt4), _ptr(out)
+  p.bias = _ptr(_f32(bias, "bias"))
+  p.lda, p.ldc_m, p.ldc_n = row_ld(x), row_ld(out), 1
+  p.M, p.N, p.K, p.batch = B * 4 * H * W, Cout, wt4.shape[2], 1
+  p.conv, p.B, p.H, p.W, p.Cin, p.OH, p.OW = 1, B, H, W, Cin, 2 * H, 2 * W
+  p.stride, p.upsample, p.no_lead_pad = 1, 2, 0
+  p.act, p.dtype, p.out_dtype, p.alpha = ACT_NONE, code(x.dtype), code(out.dtype), 1.0
+  p.tile, p.split_k = tile, split_k
+  return p
+
+
+def conv3x3_up2(x, wt4, out, bias=None, tile=0, split_k=0):
+  """conv3x3(x, wt, out, upsample=True) as four 2x2 "phase" convolutions over x itself (ldm_gemm's upsample = 2): the
+  same result up to the summation order, at 4/9 of the multiply-adds.  x [B,H,W,Cin] (channel slice allowed);
+  wt4 [4, Cout, 4*Cin] = layout.upsample_phase_kernel; out [B,2H,2W,Cout] (channel slice allowed).  Plan key: the
+  conv key with `u2` (the tables under plans/ hold nine-tap problems only: these launches run on the cost model)."""
+  _gemm(_up2_params(x, wt4, out, bias, tile, split_k), x.device)
+  return out
+
+
 def bmm_nt(a, w, out, alpha=1.0, bias=None, transposed_out=False, tile=0):
   """Batched out[b] = alpha * a[b] @ w[b]^T (+bias).  a [Bt, M, K]; w [Bt, N, K] or
   [N, K] (shared); out [Bt, M, N], or [Bt, N, ldn>=M] when transposed_out."""

@@ -18,7 +18,8 @@ changes results beyond float rounding order):
     they run for a single row;
   * cross-attention K and V of the text context (unet.py:274-275 with
     context != None) are step-invariant: `set_context` computes them once;
-  * nearest-2x upsample (unet.py:44) is fused into the following conv's gather.
+  * nearest-2x upsample (unet.py:44) is fused into the following conv, which runs as four 2x2 phase
+    convolutions over the low-resolution image with pre-summed weights (ops.conv3x3_up2).
 """
 from __future__ import annotations
 
@@ -143,7 +144,7 @@ class UNet:
                defer_reduce=True, matrix_softmax=True, gn_single_launch=True, fused_ffn=True,
                ffn_min_rows=24576, fused_tail=True, fused_xattn=True, fused_block=True,
                shared_prefix=True, merge_qkv=True, merge_qkv_max_rows=1 << 30,
-               merge_shortcut=True, merge_ffproj=True, block_min_rows=12288):
+               merge_shortcut=True, merge_ffproj=True, block_min_rows=12288, phase_upsample=True):
     # fuse_layernorm: the transformer blocks' LayerNorms come out of the producing GEMM's epilogue
     # where its tile holds whole rows (C = 320).  Measured on MI355X at R=32: 11.02 vs 10.95 ms per
     # step -- the whole-row 128x320 tile (one workgroup per CU) plus the extra epilogue pass cost
@@ -177,6 +178,9 @@ class UNet:
     # (a row limit from the first form of the launch, whose workgroups lay on one side of n_split and could not be
     # balanced at M = 32768: 6 + 3 n-tiles on 2 workgroups per panel; ranges may straddle n_split now)
     self._merge_qkv_max_rows = int(merge_qkv_max_rows)
+    # the upsample convolutions as four 2x2 phase convolutions over the image itself (ops.conv3x3_up2: 4/9 of the
+    # multiply-adds; only that weight form is built).  A/B: False = the nine-tap gather over the upsampled image
+    self._phase_upsample = bool(phase_upsample)
     self._shared_prefix = bool(shared_prefix)     # forward(paired_rows=True): the CFG pair's common prefix once (A/B: False)
     self._ctx_sel = None                  # the context rows an evaluation attends to (forward(context_rows=)); None = all
     self._pend = None
@@ -240,7 +244,8 @@ class UNet:
       p = f"output_blocks/{i}"
       up = None
       if (p + "/upsample/conv/kernel") in w:
-        up = (L.conv_kernel(w[p + "/upsample/conv/kernel"], dt, dev), L.vec(w[p + "/upsample/conv/bias"], dev))
+        mk = L.upsample_phase_kernel if self._phase_upsample else L.conv_kernel
+        up = (mk(w[p + "/upsample/conv/kernel"], dt, dev), L.vec(w[p + "/upsample/conv/bias"], dev))
       self.out_blocks.append((mk_res(p + "/residual"), mk_st(p + "/spatial_transformer"), up))
       i += 1
     assert len(self.out_blocks) == len(self.skip_ch), "U-Net skip structure mismatch"
@@ -570,7 +575,10 @@ class UNet:
             o = self._st(st, o, dst if up is None else B_.get("blk_s", shp, dt))
           if up is not None:
             self._flush()                                           # it reads o
-            ops.conv3x3(o, up[0], dst, bias=up[1], upsample=True)   # unet.py:44-47
+            if self._phase_upsample:                                # unet.py:44-47
+              ops.conv3x3_up2(o, up[0], dst, bias=up[1])
+            else:
+              ops.conv3x3(o, up[0], dst, bias=up[1], upsample=True)
         t0 = B_.get("gn", tuple(final.shape), dt)
         self._gn(final, self.gn_out, GN_EPS_RES, True, t0)
         if self.conv_out_mm is not None:
