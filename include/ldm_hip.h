@@ -536,6 +536,25 @@ int ldm_cfg_sched_update(const float* eps_all, const float* xt, float* ring, flo
                          void* stream);
 
 /*
+ * DDIM inversion, float32: the deterministic DDIM step run upwards.  coef row idx = *index is
+ * (c1, c2, a_prev, sigma) as above; xt is on the level of a_prev and the result on the level of steps[idx]:
+ *   guided != 0:  e = eps_u + guidance_scale * (eps_c - eps_u)
+ *   guided == 0:  e = eps_c, the second half of eps_all [2B][n]; the first half is NOT read (the conditional-only
+ *                 U-Net evaluation leaves it unwritten) and guidance_scale is ignored
+ *   x0  = (xt - sqrtf(1 - a_prev) * e) / sqrtf(a_prev)
+ *   xt' = (x0 + c2 * e) / c1
+ * which undoes the sigma = 0 step of ldm_cfg_ddim_update given the same e.  sigma is not read: no noise, no clip, no
+ * blend, no history.  xt_out (may be xt) receives xt', pred_x0_out (optional) x0, x_unet_out (optional) both halves
+ * concat([xt', xt']) in x_dtype.  The entry does not know which way its caller walks the table: it reads row *index
+ * and, with dec_index, decrements *index afterwards like every other update, so a caller that counts down hands in the
+ * table reversed (model_runners.py does).  n_per_sample % 4 == 0 and 16-byte aligned arrays (8-byte for a bf16
+ * x_unet_out), as ldm_cfg_ms_update.
+ */
+int ldm_cfg_ddim_invert_update(const float* eps_all, const float* xt, float* xt_out, float* pred_x0_out,
+                               void* x_unet_out, int x_dtype, const float* coef, int32_t* index, int guided,
+                               int dec_index, float guidance_scale, int B, int64_t n_per_sample, void* stream);
+
+/*
  * Panorama sampling.  A canvas [B][H][W][c] float32 is covered by nW = nY * nX windows of
  * h x w at stride (sy, sx).  Along an axis of extent L with window l and stride s (1 <= l <= L, 1 <= s <= l):
  *   n = ceil((L - l) / s) + 1,  origin_i = min(i * s, L - l)    (the last window is clamped to the edge);

@@ -222,8 +222,11 @@ __global__ void dec_index_kernel(int32_t* index) { *index = *index - 1; }
 //   kAdamsBashforth  the constants of model_runners.PLMS_WEIGHTS as (numerators) / denominator
 //   kTable           e' = sum_{m <= j} w[m] * e_{idx+m} by explicit fused multiply-adds in the order m = 0 .. j
 //                    (DESIGN.md section 10); weights == NULL: no history, ring and start are not touched
+//   kInvert          no history, and the step runs the other way: xt is on the level of a_prev,
+//                    x0 = (xt - sqrt(1 - a_prev) * e0) / sqrt(a_prev), xt' = (x0 + c2 * e0) / c1 is on the level of
+//                    steps[idx]; no sigma, noise, clip or blend.  Tables only (it draws nothing).
 // j is uniform over the launch, so a slot or a weight beyond j is never loaded (it may hold NaN).
-enum Hist { kDdim, kAdamsBashforth, kTable };
+enum Hist { kDdim, kAdamsBashforth, kTable, kInvert };
 // Where the scale of e0 = eu + gs * (ec - eu) comes from: the argument, gtab[idx], or none at all: e0 = ec and the
 // unconditional half of eps_all is never loaded.
 enum Scale { kScaleArg, kScaleTable, kCondOnly };
@@ -234,6 +237,7 @@ enum Scale { kScaleArg, kScaleTable, kCondOnly };
 template <typename TX, Hist H, Scale S, bool Rng, bool Blend>
 __global__ __launch_bounds__(256) void cfg_update4_kernel(UpdateArgs a) {
   static_assert(H != kDdim || Rng, "DDIM from tables is cfg_ddim_kernel");
+  static_assert(H != kInvert || (!Rng && !Blend && S != kScaleTable), "the inversion draws and blends nothing");
   const int idx = *a.index;
   const bool hist = H == kAdamsBashforth || (H == kTable && a.weights);
   int j = 0;
@@ -304,14 +308,18 @@ __global__ __launch_bounds__(256) void cfg_update4_kernel(UpdateArgs a) {
         for (int k = 0; k < 4; ++k) ep[k] = __builtin_fmaf(w3, h[k], ep[k]);
       }
     }
-    f32x4 x0 = c1 * x - c2 * ep;
+    f32x4 x0;
+    if constexpr (H == kInvert) x0 = (x - sb * ep) / sa;
+    else x0 = c1 * x - c2 * ep;
     if constexpr (H == kDdim) {
       if (a.clip) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) x0[k] = fminf(fmaxf(x0[k], -1.f), 1.f);
       }
     }
-    f32x4 o = sa * x0 + sb * ep;
+    f32x4 o;
+    if constexpr (H == kInvert) o = (x0 + c2 * ep) / c1;
+    else o = sa * x0 + sb * ep;
     const int64_t b = i / a.n;                         // (drawn noise: sample b, quad q of it)
     const uint32_t q = (uint32_t)((i - b * a.n) >> 2);
     if (draw_eta) {
@@ -422,6 +430,8 @@ int update_launch(const char* what, unsigned need, Hist hist, Scale scale, Updat
     case FORM(kTable, kScaleTable, 1): LAUNCH(cfg_update4_kernel, kTable, kScaleTable, true, true); break;
     case FORM(kTable, kCondOnly, 0): LAUNCH(cfg_update4_kernel, kTable, kCondOnly, false, true); break;
     case FORM(kTable, kCondOnly, 1): LAUNCH(cfg_update4_kernel, kTable, kCondOnly, true, true); break;
+    case FORM(kInvert, kScaleArg, 0): LAUNCH(cfg_update4_kernel, kInvert, kScaleArg, false, false); break;   // _invert
+    case FORM(kInvert, kCondOnly, 0): LAUNCH(cfg_update4_kernel, kInvert, kCondOnly, false, false); break;
     default: LDM_CHECK_ARG(false, "%s: no kernel for this form", what);
   }
 #undef FORM
@@ -537,6 +547,16 @@ extern "C" int ldm_cfg_sched_update(const float* eps_all, const float* xt, float
   a.bl = BlendArgs{z0, mask, q_noise, q_index_stride, q_coef, channels};
   return update_launch("ldm_cfg_sched_update", kWide | kNeedGtab, kTable, guided ? kScaleTable : kCondOnly, a, x_dtype,
                        index, dec_index, stream);
+}
+
+extern "C" int ldm_cfg_ddim_invert_update(const float* eps_all, const float* xt, float* xt_out, float* pred_x0_out,
+                                          void* x_unet_out, int x_dtype, const float* coef, int32_t* index,
+                                          int guided, int dec_index, float guidance_scale, int B,
+                                          int64_t n_per_sample, void* stream) {
+  UpdateArgs a =
+      update_base(eps_all, xt, xt_out, pred_x0_out, x_unet_out, coef, index, guidance_scale, B, n_per_sample);
+  return update_launch("ldm_cfg_ddim_invert_update", kWide, kInvert, guided ? kScaleArg : kCondOnly, a, x_dtype, index,
+                       dec_index, stream);
 }
 
 extern "C" int ldm_q_sample(const float* x0, const float* noise, int64_t noise_index_stride, const int32_t* index,

@@ -42,6 +42,11 @@ ddim_p_sample_loop_panorama samples a canvas wider than t
 crops the canvas into overlapping training-size windows (ldm_window_gather), runs the U-Net on the window rows,
 averages the windows' eps back onto the canvas (ldm_window_fold) and runs the configured solver's one update launch
 on the canvas.  The updates are affine in eps, so that equals averaging the windows' step outputs (MultiDiffusion).
+
+ddim_invert_loop runs the deterministic DDIM step upwards from the latents of an image: a U-Net
+evaluation at the level the input is on and one update launch (ldm_cfg_ddim_invert_update) per step, replayed from a
+captured graph of its own.  ddim_p_sample_loop(x_T=, start_index=k) samples from the level it reached, and
+ddim_p_sample_loop_edit chains the two: inversion under a source prompt, sampling under a target prompt.
 """
 from __future__ import annotations
 
@@ -469,6 +474,10 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     self._gtab = None
     self._plms_tbl = None
     self._form_events = None
+    self._inv_graph = None                       # the inversion's captured step: it coexists
+    self._inv_graph_key = None                   # with the sampling graphs above
+    self._inv_tbl = None
+    self._inv_temb = None
     self.last_step_ms = None
 
   # ---- the steps' temb projections, once per sampler ---------------------------------
@@ -512,6 +521,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     """A buffer the captured steps read has a new address."""
     self._graph = None
     self._sched_graphs = {}
+    self._inv_graph = None
 
   def _set_loop_start(self, start_index):
     """PLMS / DEIS: the loop's first step is the one at DDIM index `start_index` (it has no history)."""
@@ -758,17 +768,18 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     """Noise source "device" and no per-step table given: the step's update launch draws what it needs."""
     return self._noise_source == "device" and noises is None and q_noises is None
 
-  def _sample_loop(self, num_steps, reset, step, gkey, record):
+  def _sample_loop(self, num_steps, reset, step, gkey, record, slot="_graph"):
     """Run `num_steps` DDIM steps from the state `reset()` sets (latents, U-Net input and the device counter at
     _loop_start_index(num_steps)); `step(dec_index)` enqueues one step.  With graphs (and no `record`) one step
     is captured once per `gkey` -- after a warm-up step on a side stream has allocated every scratch buffer --
-    and replayed num_steps times; the counter lives on the device, so the graph serves any start index."""
+    and replayed num_steps times; the counter lives on the device, so the graph serves any start index.  `slot`: the
+    attribute that keeps the graph (its key in `slot`_key): a loop with a slot of its own does not evict the others'."""
     reset()
     use_graph = self._use_graph and record is None
     t0 = torch.cuda.Event(enable_timing=True)
     t1 = torch.cuda.Event(enable_timing=True)
     if use_graph:
-      if self._graph is None or self._graph_key != gkey:
+      if getattr(self, slot) is None or getattr(self, slot + "_key") != gkey:
         self._index_dev.fill_(num_steps - 1)         # (the warm-up step does not move the counter)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -782,11 +793,13 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
         # while this thread captures; only this thread's calls belong to the capture
         with torch.cuda.graph(g, capture_error_mode="thread_local"):
           step(True)
-        self._graph, self._graph_key = g, gkey
+        setattr(self, slot, g)
+        setattr(self, slot + "_key", gkey)
         reset()
+      graph = getattr(self, slot)
       t0.record()
       for _ in range(num_steps):                                          # :484-502
-        self._graph.replay()
+        graph.replay()
       t1.record()
     else:
       t0.record()
@@ -797,19 +810,49 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       t1.record()
     self._loop_events = (t0, t1, num_steps)
 
+  def _denoise(self, k, set_start, guidance_scale, gsched, noise_table, masked, rng, record):
+    """DDIM indices k-1 .. 0 of the configured solver from the latents `set_start()` leaves in _xt / _x2 (what
+    ddim_p_sample_loop, its start_index= form and the img2img loop share); returns the decoded images."""
+    def reset():
+      set_start()
+      self._index_dev.fill_(self._loop_start_index(k))                    # :476 (index = k - 1 in the first step)
+      self._set_loop_start(k - 1)
+
+    if gsched is not None:
+      self._sample_loop_sched(self._sched_forms(gsched, k - 1, k), reset,
+                              lambda guided, dec: self._step_sched(guided, dec, masked=masked, rng=rng),
+                              self._sched_key_of(masked, rng), record)
+      return self._finish(self._xt)
+    gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, masked, self._noise_source, rng,
+            self._step_spacing, self._sampler)
+    self._sample_loop(k, reset, lambda dec: self._step(guidance_scale, False, noise_table, dec_index=dec,
+                                                        masked=masked, rng=rng), gkey, record)
+    return self._finish(self._xt)
+
   def ddim_p_sample_loop(self, cond_model_inputs, shape, guidance_scale=5., x_T=None,
-                         noises=None, seed=0, first_sample_index=0, record=None, guidance_interval=None):
+                         noises=None, seed=0, first_sample_index=0, record=None, guidance_interval=None,
+                         start_index=None):
     """model_runners.py:474-509.  Extra inputs the reference lacks: `x_T` [B,h,w,4]
     (else N(0,1) from `seed`, keyed per global sample index), `noises` [N,B,h,w,4]
     indexed by DDIM index (only read when eta > 0), `record` (list: receives x_t
     after every step -- disables graph replay).  noise_source="device": what the caller
     does not give is drawn on the device; without `noises` no table exists.
     `guidance_scale` may be N floats indexed by DDIM index, or a float with `guidance_interval` = (t_lo, t_hi) in
-    training timesteps (guided where t_lo <= steps[i] <= t_hi); DESIGN.md section 11, eta = 0 only."""
+    training timesteps (guided where t_lo <= steps[i] <= t_hi); DESIGN.md section 11, eta = 0 only.
+    `start_index` = k in [1, N]: `x_T` (required) lies on the level of steps[k-1], what
+    ddim_invert_loop returns, and the loop runs DDIM indices k-1 .. 0 only, a multistep solver without history at
+    its first step; tables and schedules stay indexed by DDIM index.  None: all N steps."""
     gsched = self._guidance(guidance_scale, guidance_interval)
     B, h, w, c = (int(s) for s in shape)
-    context = self._cond_stage_model(cond_model_inputs)                   # :475
     n = len(self._ddim_steps)
+    k = n
+    if start_index is not None:
+      k = int(start_index)
+      if x_T is None:
+        raise ValueError("start_index needs x_T: the latents on the level of steps[start_index - 1]")
+      if k != start_index or not 1 <= k <= n:
+        raise ValueError(f"start_index must be an int in [1, {n}], got {start_index!r}")
+    context = self._cond_stage_model(cond_model_inputs)                   # :475
     xt = self._x_T(x_T, seed, first_sample_index, B, h, w, c)
     # :480-482 concat(context[:4], context[4:]) == context
     cond_combined = context
@@ -817,22 +860,8 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     self._set_context(cond_combined)
     rng = self._draws_on_device(noises)
     noise_table = None if rng else self._eta_noise_table(noises, seed, first_sample_index, B, h, w, c)
-
-    def reset():
-      self._set_x_T(xt, seed, first_sample_index, B)
-      self._index_dev.fill_(self._loop_start_index(n))                    # :476 (index = N - 1 in the first step)
-      self._set_loop_start(n - 1)
-
-    if gsched is not None:
-      self._sample_loop_sched(self._sched_forms(gsched, n - 1, n), reset,
-                              lambda guided, dec: self._step_sched(guided, dec, rng=rng),
-                              self._sched_key_of(False, rng), record)
-      return self._finish(self._xt)
-    gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, False, self._noise_source, rng,
-            self._step_spacing, self._sampler)
-    self._sample_loop(n, reset, lambda dec: self._step(guidance_scale, False, noise_table, dec_index=dec, rng=rng),
-                      gkey, record)
-    return self._finish(self._xt)
+    return self._denoise(k, lambda: self._set_x_T(xt, seed, first_sample_index, B), guidance_scale, gsched,
+                         noise_table, False, rng, record)
 
   def _x_T(self, x_T, seed, first_sample_index, B, h, w, c):
     """The caller's x_T on the device; drawn on the host when omitted; None (noise source "device") = drawn on the
@@ -885,18 +914,13 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     n = len(self._ddim_steps)
     k = img2img_start(strength, n)
     B = len(cond_model_inputs) // 2
-    imgs = torch.as_tensor(np.asarray(init_images) if not isinstance(init_images, torch.Tensor) else init_images,
-                           dtype=torch.float32)
-    if imgs.dim() == 3:
-      imgs = imgs[None].expand(B, *imgs.shape)
-    if imgs.dim() != 4 or imgs.shape[0] != B or imgs.shape[-1] != 3:
-      raise ValueError(f"init_images must be [B={B},H,W,3] or [H,W,3], got {tuple(imgs.shape)}")
+    imgs = self._init_images(init_images, B)
     if mask is not None:
       mask = torch.as_tensor(np.asarray(mask) if not isinstance(mask, torch.Tensor) else mask, dtype=torch.float32)
       if mask.dim() == 2:
         mask = mask[None].expand(B, *mask.shape)
     context = self._cond_stage_model(cond_model_inputs)
-    z0 = self.get_latents(imgs.contiguous(), noise=encode_noise, seed=seed, first_sample_index=first_sample_index)
+    z0 = self.get_latents(imgs, noise=encode_noise, seed=seed, first_sample_index=first_sample_index)
     _, h, w, c = z0.shape
     if mask is not None and tuple(mask.shape) != (B, h, w):
       raise ValueError(f"mask must be [B,h,w] = {(B, h, w)} (or [h,w]) at latent resolution, "
@@ -922,26 +946,138 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     sa, sb, _ = self._device_q_tables()
     masked = mask is not None
 
-    def reset():
+    def set_start():
       if self._noise_source == "device":
         self._set_rng(seed, first_sample_index)
       if rng:
         ops.q_sample_rng(z0_buf, self._rng, Q_STREAM + k - 1, t_start, sa, sb, self._xt, x_unet_out=self._x2)
       else:
         ops.q_sample(z0_buf, q_buf[k - 1], t_start, sa, sb, self._xt, x_unet_out=self._x2)
-      self._index_dev.fill_(self._loop_start_index(k))
-      self._set_loop_start(k - 1)
 
-    if gsched is not None:
-      self._sample_loop_sched(self._sched_forms(gsched, k - 1, k), reset,
-                              lambda guided, dec: self._step_sched(guided, dec, masked=masked, rng=rng),
-                              self._sched_key_of(masked, rng), record)
-      return self._finish(self._xt)
-    gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, masked, self._noise_source, rng,
-            self._step_spacing, self._sampler)
-    self._sample_loop(k, reset, lambda dec: self._step(guidance_scale, False, noise_table, dec_index=dec,
-                                                        masked=masked, rng=rng), gkey, record)
-    return self._finish(self._xt)
+    return self._denoise(k, set_start, guidance_scale, gsched, noise_table, masked, rng, record)
+
+  def _init_images(self, init_images, B):
+    """init_images [B,H,W,3] (or [H,W,3], tiled over the batch) as a contiguous float32 tensor."""
+    imgs = torch.as_tensor(np.asarray(init_images) if not isinstance(init_images, torch.Tensor) else init_images,
+                           dtype=torch.float32)
+    if imgs.dim() == 3:
+      imgs = imgs[None].expand(B, *imgs.shape)
+    if imgs.dim() != 4 or imgs.shape[0] != B or imgs.shape[-1] != 3:
+      raise ValueError(f"init_images must be [B={B},H,W,3] or [H,W,3], got {tuple(imgs.shape)}")
+    return imgs.contiguous()
+
+  # ---- DDIM inversion (DESIGN.md section 13) ---------------------------------------------------
+  def inversion_timesteps(self):
+    """t_in [N] int32: the training timestep of the level below DDIM index i, where the inversion step at index i
+    evaluates the U-Net: t_in[0] = 0, t_in[i] = steps[i-1], so that abar[t_in[i]] == a_prev[i]."""
+    return np.concatenate([[0], self._ddim_steps[:-1]]).astype(np.int32)
+
+  def _invert_tables(self):
+    """The inversion's own device tables, made on first use.  The loop counter only ever walks down (the U-Net's
+    first launch pre-decrements it), so both tables are stored reversed: row N-1-i holds inversion index i.  (coef
+    rows, t_in as the step table of the four temb launches)."""
+    if self._inv_tbl is None:
+      t_rev = np.ascontiguousarray(self.inversion_timesteps()[::-1])
+      self._inv_tbl = (self._coef_dev.flip(0).contiguous(), torch.from_numpy(t_rev).to(self.device))
+    return self._inv_tbl
+
+  def _invert_temb_kwargs(self, dec_index):
+    """_temb_kwargs for an inversion step: the temb table of the reversed t_in (built on first use)."""
+    if self._inv_temb is None and hasattr(self._unet, "temb_table") and self._use_temb_table:
+      self._inv_temb = self._unet.temb_table(self._invert_tables()[1]).clone()
+    self._pre_dec = self._inv_temb is not None
+    if self._inv_temb is None:
+      return {}
+    return dict(temb_table=self._inv_temb, pre_decrement=bool(dec_index))
+
+  def _invert_counter_start(self):
+    """Value of the device counter before the first inversion step, whatever the depth: the step at inversion index
+    i reads row N-1-i, and a pre-decrementing step starts one above its row.  After k steps it holds this - k."""
+    self._invert_temb_kwargs(True)
+    n = len(self._ddim_steps)
+    return n if self._pre_dec else n - 1
+
+  def _step_invert(self, guidance_scale, dec_index, pred_x0_out=None):
+    """One inversion step: the U-Net at t_in on the level x is on, then ldm_cfg_ddim_invert_update.  A scale of
+    exactly 1 with skip_unguided: the conditional rows x2[B:] against the resident context's rows B .. 2B-1 and the
+    conditional-only update; else the paired 2B rows and the scaled update.  Either writes both halves of x2."""
+    B = self._xt.shape[0]
+    coef, t_rev = self._invert_tables()
+    cond_only = float(guidance_scale) == 1. and self._skip_unguided
+    kw = self._invert_temb_kwargs(dec_index)
+    if cond_only:
+      self._unet.forward(self._x2[B:], steps=t_rev, index=self._index_dev, out=self._eps[B:], paired_rows=False,
+                         context_rows=(B, 2 * B), **kw)
+    else:
+      self._unet.forward(self._x2, steps=t_rev, index=self._index_dev, out=self._eps, paired_rows=True, **kw)
+    ops.cfg_ddim_invert_update(self._eps, self._xt, self._xt, coef, self._index_dev, not cond_only, guidance_scale,
+                               x_unet_out=self._x2, dec_index=dec_index and not self._pre_dec,
+                               pred_x0_out=pred_x0_out)
+
+  def ddim_invert_loop(self, cond_model_inputs, init_images=None, latents=None, guidance_scale=1., strength=1.,
+                       encode_noise=None, seed=0, first_sample_index=0, record=None):
+    """DDIM inversion: the deterministic, first-order DDIM ODE run upwards from z0, whatever
+    sampler= and eta the sampler was built with.  cond_model_inputs: token ids [uncond x B; cond x B].  Exactly one
+    of `init_images` ([B,H,W,3] or [H,W,3], tiled; float32 in [-1, 1]; z0 = get_latents(init_images, encode_noise))
+    and `latents` (z0 [B,h,w,c], already scaled).  k = int(strength * N) as for img2img; the loop runs inversion
+    indices 0 .. k-1: e = eps(x, t_in[i]) with the guidance scale (1: the conditional eps alone), x0 = (x -
+    sqrt(1 - a_prev[i]) e) / sqrt(a_prev[i]), x <- (x0 + c2[i] e) / c1[i].  `record` receives x after each step
+    (eager, no graph).  Returns the latents on the level of steps[k-1], float32 [B,h,w,c] on the device (a copy;
+    they also stay in self._xt): ddim_p_sample_loop(x_T=, start_index=k) maps them back."""
+    if np.ndim(guidance_scale) > 0:
+      raise ValueError("the inversion loop takes one float guidance_scale: a guidance schedule is not supported")
+    if (init_images is None) == (latents is None):
+      raise ValueError("ddim_invert_loop needs exactly one of init_images and latents")
+    guidance_scale = float(guidance_scale)
+    k = img2img_start(strength, len(self._ddim_steps))
+    B = len(cond_model_inputs) // 2
+    context = self._cond_stage_model(cond_model_inputs)
+    if latents is None:
+      z0 = self.get_latents(self._init_images(init_images, B), noise=encode_noise, seed=seed,
+                            first_sample_index=first_sample_index)
+    else:
+      z0 = torch.as_tensor(np.asarray(latents) if not isinstance(latents, torch.Tensor) else latents,
+                           dtype=torch.float32)
+      if z0.dim() != 4 or z0.shape[0] != B:
+        raise ValueError(f"latents must be [B={B},h,w,c], got {tuple(z0.shape)}")
+    _, h, w, c = z0.shape
+    self._alloc_state(B, h, w, c)
+    self._set_context(context)
+    z0_buf = self._owned("_z0_buf", z0, (B, h, w, c))
+    self._invert_tables()                      # (made before any capture: the graph reads them at fixed addresses)
+
+    def reset():
+      self._xt.copy_(z0_buf)
+      self._x2[:B].copy_(z0_buf)
+      self._x2[B:].copy_(z0_buf)
+      self._index_dev.fill_(self._invert_counter_start())
+
+    cond_only = guidance_scale == 1. and self._skip_unguided
+    # (the scale is an argument of the captured launch, and the conditional-only form has none; the depth k is not
+    # in the key: the counter is on the device)
+    gkey = ("invert", None if cond_only else guidance_scale, self._ctx_shape, self._step_spacing)
+    self._sample_loop(k, reset, lambda dec: self._step_invert(guidance_scale, dec), gkey, record, slot="_inv_graph")
+    return self._xt.clone()
+
+  def ddim_p_sample_loop_edit(self, source_inputs, target_inputs, init_images, guidance_scale=5., strength=0.75,
+                              invert_guidance_scale=1., encode_noise=None, noises=None, seed=0, first_sample_index=0,
+                              record=None, guidance_interval=None):
+    """Prompt editing of a real image: z0 = get_latents(init_images); k = int(strength * N)
+    inversion steps under the source prompt (`source_inputs`, scale `invert_guidance_scale`); then DDIM indices
+    k-1 .. 0 of the configured solver under the target prompt (`target_inputs`, `guidance_scale` /
+    `guidance_interval` as in ddim_p_sample_loop).  Both id arrays are [uncond x B; cond x B].  With the same ids and
+    both scales 1 this reconstructs the image.  `record` receives x after each sampling step.  Returns the decoded
+    images; the final latents stay in self._xt."""
+    if np.shape(source_inputs) != np.shape(target_inputs):
+      raise ValueError(f"source_inputs {np.shape(source_inputs)} and target_inputs {np.shape(target_inputs)} must "
+                       "have the same shape")
+    k = img2img_start(strength, len(self._ddim_steps))
+    x = self.ddim_invert_loop(source_inputs, init_images=init_images, guidance_scale=invert_guidance_scale,
+                              strength=strength, encode_noise=encode_noise, seed=seed,
+                              first_sample_index=first_sample_index)
+    return self.ddim_p_sample_loop(target_inputs, tuple(x.shape), guidance_scale, x_T=x, noises=noises, seed=seed,
+                                   first_sample_index=first_sample_index, record=record,
+                                   guidance_interval=guidance_interval, start_index=k)
 
   # ---- panorama (DESIGN.md section 12) ---------------------------------------------------------
   def _alloc_windows(self, B, n_win, h, w, c):

@@ -21,7 +21,7 @@ __all__ = [
     "bmm_nt", "conv3x3_small", "groupnorm", "layernorm", "softmax_rows", "attention",
     "time_embedding", "gemv", "cfg_ddim_update", "cfg_ddim_update_masked", "cfg_plms_update", "q_sample",
     "philox_u32", "normal_fill", "q_sample_rng", "cfg_ddim_update_rng", "cfg_plms_update_rng", "cfg_ms_update",
-    "cfg_ms_update_rng", "cfg_sched_update", "window_gather", "window_fold", "post_quant", "vq_nearest", "embedding",
+    "cfg_ms_update_rng", "cfg_sched_update", "cfg_ddim_invert_update", "window_gather", "window_fold", "post_quant", "vq_nearest", "embedding",
     "minmax_u8", "cast",
 ]
 
@@ -1020,6 +1020,21 @@ def cfg_sched_update(eps_all, xt, xt_out, coef, gtab, index, guided, ring=None, 
       int(bool(dec_index)), B, n,
       *_blend_args(xt, coef, z0, mask, q_coef, q_noise, q_index_stride, table=rng is None), _stream()),
         "ldm_cfg_sched_update")
+  return xt_out
+
+
+def cfg_ddim_invert_update(eps_all, xt, xt_out, coef, index, guided, guidance_scale=1., x_unet_out=None,
+                           dec_index=False, pred_x0_out=None):
+  """The DDIM step run upwards (include/ldm_hip.h): xt on the level of a_prev = coef[*index, 2]
+  -> xt_out on the level of steps[*index].  `guided` False: eps is the conditional half eps_all[B:], the other half
+  is not read and `guidance_scale` is ignored.  No noise, clip, history or blend."""
+  B, n, xd = _update_dims(xt, index, x_unet_out)
+  assert eps_all.is_contiguous() and eps_all.numel() == 2 * xt.numel()
+  assert xt_out.numel() == xt.numel() and (pred_x0_out is None or pred_x0_out.numel() == xt.numel())
+  assert x_unet_out is None or (x_unet_out.is_contiguous() and x_unet_out.numel() == 2 * xt.numel())
+  check(lib.ldm_cfg_ddim_invert_update(
+      *_update_ptrs(eps_all, xt, (), xt_out, pred_x0_out, x_unet_out, xd, coef, index), int(bool(guided)),
+      int(bool(dec_index)), float(guidance_scale), B, n, _stream()), "ldm_cfg_ddim_invert_update")
   return xt_out
 
 

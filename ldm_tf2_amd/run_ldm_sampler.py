@@ -43,6 +43,12 @@ Panorama: optional `ldm_sampling` keys `window: [h, w]` and `window_stride: [sy,
 `window`-sized crops of the canvas and averages their predictions where they overlap (MultiDiffusion; DESIGN.md
 section 12).  Every solver, step table and noise source runs; `init_image`, `mask`, `sample_save_progress`,
 `guidance_interval` and a list `guidance_scale` cannot be combined with it.  Without `window` nothing changes.
+
+Prompt editing: optional `ldm_sampling` key `source_prompt` (a string; needs `init_image`).  The init image is encoded,
+inverted `int(strength * N)` DDIM steps under `source_prompt` (DDIM inversion, guidance scale `invert_guidance_scale`,
+default 1) and sampled back under `text_prompt`, the target, with `guidance_scale`.  The same
+prompt twice with both scales 1 reconstructs the image.  `mask`, `window` and `sample_save_progress` cannot be combined
+with it.  Without `source_prompt` nothing changes.
 """
 from __future__ import annotations
 
@@ -156,10 +162,40 @@ def panorama_kwargs(config, seed):
   return dict(window=window, stride=stride, seed=seed)
 
 
-def sampling_call(config, token_ids, seed):
-  """(sampler method name, positional args, kwargs) of the call main() makes for `config`."""
+def _init_images(samp):
+  """`ldm_sampling.init_image`: a .npy of uint8 [H,W,3] or [B,H,W,3], read as x / 127.5 - 1."""
+  img = np.load(samp["init_image"])
+  if img.dtype != np.uint8 or img.ndim not in (3, 4) or img.shape[-1] != 3:
+    raise ValueError(f"init_image must be uint8 [H,W,3] or [B,H,W,3], got {img.dtype} {img.shape}")
+  return img.astype(np.float32) / np.float32(127.5) - np.float32(1.0)
+
+
+def edit_call(config, token_ids, source_ids, seed):
+  """`ldm_sampling.source_prompt` (the reference's YAML has no such key): the edit loop's call.
+  `source_ids`: the source prompt's token ids, laid out like `token_ids` (the target's)."""
+  samp = config["ldm_sampling"]
+  if not isinstance(samp["source_prompt"], str):
+    raise ValueError(f"ldm_sampling.source_prompt must be a string, got {samp['source_prompt']!r}")
+  for key in ("mask", "window", "sample_save_progress"):
+    if samp.get(key) is not None and samp.get(key) is not False:
+      raise ValueError(f"ldm_sampling.source_prompt cannot be combined with ldm_sampling.{key}")
+  if not samp.get("init_image"):
+    raise ValueError("ldm_sampling.source_prompt needs ldm_sampling.init_image")
+  if source_ids is None:
+    raise ValueError("ldm_sampling.source_prompt is set: its token ids are needed")
+  kwargs = dict(strength=float(samp.get("strength", 0.75)),
+                invert_guidance_scale=float(samp.get("invert_guidance_scale", 1.)), seed=seed,
+                **guidance_kwargs(config))
+  return "ddim_p_sample_loop_edit", (source_ids, token_ids, _init_images(samp), samp["guidance_scale"]), kwargs
+
+
+def sampling_call(config, token_ids, seed, source_ids=None):
+  """(sampler method name, positional args, kwargs) of the call main() makes for `config`.  `source_ids`: the token
+  ids of `ldm_sampling.source_prompt` when the key is there."""
   samp = config["ldm_sampling"]
   base = (token_ids, samp["latent_shape"], samp["guidance_scale"])
+  if samp.get("source_prompt") is not None:
+    return edit_call(config, token_ids, source_ids, seed)
   if samp.get("window") is not None:
     return "ddim_p_sample_loop_panorama", base, panorama_kwargs(config, seed)
   if samp.get("mask") is not None and not samp.get("init_image"):
@@ -167,10 +203,7 @@ def sampling_call(config, token_ids, seed):
   if samp.get("init_image"):
     if samp.get("sample_save_progress"):
       raise ValueError("sample_save_progress is not supported with init_image")
-    img = np.load(samp["init_image"])
-    if img.dtype != np.uint8 or img.ndim not in (3, 4) or img.shape[-1] != 3:
-      raise ValueError(f"init_image must be uint8 [H,W,3] or [B,H,W,3], got {img.dtype} {img.shape}")
-    images = img.astype(np.float32) / np.float32(127.5) - np.float32(1.0)
+    images = _init_images(samp)
     kwargs = dict(strength=float(samp.get("strength", 0.75)), seed=seed, **guidance_kwargs(config))
     if samp.get("mask") is not None:
       pm = np.load(samp["mask"])
@@ -239,7 +272,11 @@ def main(argv=None):
   samp = config["ldm_sampling"]
   token_ids = get_token_ids(samp["text_prompt"], samp["latent_shape"][0], samp["vocab_dir"],
                             config["cond_stage_model"]["max_seq_len"])
-  method, args_, kwargs = sampling_call(config, token_ids, args.seed)
+  source_ids = None
+  if samp.get("source_prompt") is not None:
+    source_ids = get_token_ids(samp["source_prompt"], samp["latent_shape"][0], samp["vocab_dir"],
+                               config["cond_stage_model"]["max_seq_len"])
+  method, args_, kwargs = sampling_call(config, token_ids, args.seed, source_ids=source_ids)
   if method == "ddim_p_sample_loop_progressive":
     # run_ldm_sampler.py:89-94 (with the reference's unpacking bug fixed: three results)
     _, sample_prog, pred_x0_prog = sampler.ddim_p_sample_loop_progressive(*args_, **kwargs)
