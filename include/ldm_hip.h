@@ -579,6 +579,29 @@ int ldm_window_gather(const float* canvas, void* x_win, int x_dtype, int B, int 
 int ldm_window_fold(const float* eps_win, float* eps_canvas, int halves, int B, int H, int W, int c, int h, int w,
                     int sy, int sx, void* stream);
 
+/*
+ * Latent resize: x [B][H][W][c] float32 -> out [B][Ho][Wo][c] float32, enlarging or shrinking,
+ * no antialiasing.  Per axis, with source extent L, output extent Lo and output index i:
+ *   LDM_RESIZE_NEAREST:  the source index min((i * L) / Lo, L - 1) in integer arithmetic (i / 2 at 2x); the output is
+ *                        a copy of the source bits.
+ *   LDM_RESIZE_BILINEAR: s = max((i + 0.5) L / Lo - 0.5, 0), i0 = floor(s), f = s - i0; taps min(i0, L - 1) and
+ *                        min(i0 + 1, L - 1) with the weights 1 - f and f.
+ *   LDM_RESIZE_BICUBIC:  s = (i + 0.5) L / Lo - 0.5, i0 = floor(s), f = s - i0; taps clamp(i0 - 1 .. i0 + 2, 0, L - 1)
+ *                        with the weights of Keys' kernel, a = -0.75, at the distances f + 1, f, 1 - f, 2 - f.
+ * These are the align_corners = False rules.  s is formed exactly, as the integer (2 i + 1) L - Lo over 2 Lo, and f by
+ * one correctly rounded float32 division; the weights and the sum over the tap grid of wy * wx * x (rows outermost,
+ * acc = fma(wy * wx, x, acc) in both paths) are float32.  Taps and weights are computed in the kernel from (L, Lo, i): there is no device table.  A thread owns
+ * an output pixel: no atomics, the result is deterministic.  Ho == H && Wo == W copies the bits in every mode.
+ *
+ * c % 4 == 0 with 16-byte aligned pointers moves one channel quad per thread in 16-byte accesses; any other c >= 1,
+ * or a pointer aligned to its element only, takes an element-wise path with the same results.  LDM_ERR_ARG: a null
+ * pointer, an unknown mode, or an extent, B or c below 1.
+ */
+#define LDM_RESIZE_NEAREST 0
+#define LDM_RESIZE_BILINEAR 1
+#define LDM_RESIZE_BICUBIC 2
+int ldm_resize_nhwc(const float* x, float* out, int B, int H, int W, int c, int Ho, int Wo, int mode, void* stream);
+
 /* decode_first_stage prologue (model_runners.py:426 + autoencoder.py:362,434):
  * out = Dense_{C->C}(latents / scale_factor), C <= 8; float32 in, out_dtype out. */
 int ldm_post_quant(const float* latents, float scale_factor, const float* kernel_io,

@@ -47,6 +47,11 @@ ddim_invert_loop runs the deterministic DDIM step upwards
 evaluation at the level the input is on and one update launch (ldm_cfg_ddim_invert_update) per step, replayed from a
 captured graph of its own.  ddim_p_sample_loop(x_T=, start_index=k) samples from the level it reached, and
 ddim_p_sample_loop_edit chains the two: inversion under a source prompt, sampling under a target prompt.
+
+ddim_p_sample_loop_hires samples at the U-Net's training size, resizes the latents on the device
+(ldm_resize_nhwc) and re-runs the last int(strength * N) DDIM indices at the larger size, the unmasked img2img loop
+without an encoder.  The sampler keeps the device state and the captured graphs of every latent shape it has run
+(_alloc_state), so the two passes of a call, and later calls, replay two graphs captured once.
 """
 from __future__ import annotations
 
@@ -95,6 +100,15 @@ Q_STREAM = (1 << 30) + 1         # + i: forward-diffusion noise Q[i] of DDIM ind
 XT_STREAM = 0                    # x_T
 ETA_STREAM = 1 << 29             # + i: eta noise of the step at DDIM index i
 NOISE_SOURCES = ("host", "device")
+RESIZE_MODES = ("nearest", "bilinear", "bicubic")
+
+
+def hires_seed(seed):
+  """The seed of everything the second pass of ddim_p_sample_loop_hires draws: `seed` mod 2^64
+  with bit 63 flipped.  It is a 64-bit value that differs from `seed` by at least 2^63, so on the host no generator key
+  of the second pass ((s', index, Q_STREAM + i) and (s' + 1 + i, index), i < N) equals one of the first ((seed, index)
+  and (seed + 1 + i, index)), and on the device the two passes run under different Philox keys."""
+  return (int(seed) % (1 << 64)) ^ (1 << 63)
 STEP_SPACINGS = ("uniform", "logsnr", "karras")
 KARRAS_RHO = 7.
 
@@ -467,6 +481,8 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     self._pre_dec = False
     self._verbose = verbose
     self._skip_unguided = bool(skip_unguided)    # A/B: False = an unguided step still evaluates all 2B rows
+    self._states = {}                            # (B,h,w,c) -> the device state and captured graphs of a shape
+    self._state_key = None                       # that is not the current one (_alloc_state)
     self._graph = None
     self._graph_key = None
     self._sched_graphs = {}                      # guidance schedules: form (guided?) -> captured step
@@ -498,9 +514,30 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     return n if self._pre_dec else n - 1
 
   # ---- one step on device state -----------------------------------------------------
+  # What belongs to one latent shape (B,h,w,c): the step's state, the buffers the sampler owns and the window batch
+  # (all sized by the shape), and the graphs captured over them.  The attributes hold the CURRENT shape's; the others'
+  # wait in _states, so a sampler that alternates between two shapes allocates and captures each
+  # once.  What the graphs of every shape read alike (_rng, _gtab, the tables, the device counter) is not listed.
+  _SHAPE_BUFFERS = ("_xt", "_x2", "_eps", "_ring", "_start", "_noise_buf", "_q_buf", "_z0_buf", "_mask_buf", "_t_buf",
+                    "_x_win", "_eps_win", "_win_key")
+  _SHAPE_GRAPHS = ("_graph", "_graph_key", "_sched_graphs", "_sched_key", "_inv_graph", "_inv_graph_key")
+
   def _alloc_state(self, B, h, w, c):
     key = (B, h, w, c)
-    if getattr(self, "_state_key", None) != key:
+    if self._state_key != key:
+      names = self._SHAPE_BUFFERS + self._SHAPE_GRAPHS
+      if self._state_key is not None:
+        self._states[self._state_key] = {n: getattr(self, n) for n in names if hasattr(self, n)}
+      saved = self._states.pop(key, None)
+      for n in self._SHAPE_BUFFERS:
+        if hasattr(self, n):
+          delattr(self, n)
+      if saved is not None:                      # a shape seen before: its buffers and graphs as they were left
+        for n, v in saved.items():
+          setattr(self, n, v)
+        self._state_key = key
+        return
+      self._graph_key = self._sched_key = self._inv_graph_key = None
       dev, f32 = self.device, torch.float32
       self._xt = torch.empty(B, h, w, c, dtype=f32, device=dev)
       self._x2 = torch.empty(2 * B, h, w, c, dtype=f32, device=dev)
@@ -517,8 +554,12 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       self._state_key = key
       self._drop_graphs()
 
+  def release_shapes(self):
+    """Frees the state and graphs kept for every latent shape but the current one."""
+    self._states = {}
+
   def _drop_graphs(self):
-    """A buffer the captured steps read has a new address."""
+    """A buffer the captured steps of the current shape read has a new address."""
     self._graph = None
     self._sched_graphs = {}
     self._inv_graph = None
@@ -810,9 +851,10 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       t1.record()
     self._loop_events = (t0, t1, num_steps)
 
-  def _denoise(self, k, set_start, guidance_scale, gsched, noise_table, masked, rng, record):
+  def _denoise(self, k, set_start, guidance_scale, gsched, noise_table, masked, rng, record, decode=True):
     """DDIM indices k-1 .. 0 of the configured solver from the latents `set_start()` leaves in _xt / _x2 (what
-    ddim_p_sample_loop, its start_index= form and the img2img loop share); returns the decoded images."""
+    ddim_p_sample_loop, its start_index= form and the img2img loop share); returns the decoded images, or with
+    decode=False the latents (_xt itself: the current shape's state)."""
     def reset():
       set_start()
       self._index_dev.fill_(self._loop_start_index(k))                    # :476 (index = k - 1 in the first step)
@@ -822,12 +864,12 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       self._sample_loop_sched(self._sched_forms(gsched, k - 1, k), reset,
                               lambda guided, dec: self._step_sched(guided, dec, masked=masked, rng=rng),
                               self._sched_key_of(masked, rng), record)
-      return self._finish(self._xt)
+      return self._finish(self._xt) if decode else self._xt
     gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, masked, self._noise_source, rng,
             self._step_spacing, self._sampler)
     self._sample_loop(k, reset, lambda dec: self._step(guidance_scale, False, noise_table, dec_index=dec,
                                                         masked=masked, rng=rng), gkey, record)
-    return self._finish(self._xt)
+    return self._finish(self._xt) if decode else self._xt
 
   def ddim_p_sample_loop(self, cond_model_inputs, shape, guidance_scale=5., x_T=None,
                          noises=None, seed=0, first_sample_index=0, record=None, guidance_interval=None,
@@ -843,7 +885,6 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     ddim_invert_loop returns, and the loop runs DDIM indices k-1 .. 0 only, a multistep solver without history at
     its first step; tables and schedules stay indexed by DDIM index.  None: all N steps."""
     gsched = self._guidance(guidance_scale, guidance_interval)
-    B, h, w, c = (int(s) for s in shape)
     n = len(self._ddim_steps)
     k = n
     if start_index is not None:
@@ -853,6 +894,12 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       if k != start_index or not 1 <= k <= n:
         raise ValueError(f"start_index must be an int in [1, {n}], got {start_index!r}")
     context = self._cond_stage_model(cond_model_inputs)                   # :475
+    return self._sample_from(context, shape, k, guidance_scale, gsched, x_T, noises, seed, first_sample_index, record)
+
+  def _sample_from(self, context, shape, k, guidance_scale, gsched, x_T, noises, seed, first_sample_index, record,
+                   decode=True):
+    """ddim_p_sample_loop from the text context on: DDIM indices k-1 .. 0 from x_T."""
+    B, h, w, c = (int(s) for s in shape)
     xt = self._x_T(x_T, seed, first_sample_index, B, h, w, c)
     # :480-482 concat(context[:4], context[4:]) == context
     cond_combined = context
@@ -861,7 +908,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     rng = self._draws_on_device(noises)
     noise_table = None if rng else self._eta_noise_table(noises, seed, first_sample_index, B, h, w, c)
     return self._denoise(k, lambda: self._set_x_T(xt, seed, first_sample_index, B), guidance_scale, gsched,
-                         noise_table, False, rng, record)
+                         noise_table, False, rng, record, decode=decode)
 
   def _x_T(self, x_T, seed, first_sample_index, B, h, w, c):
     """The caller's x_T on the device; drawn on the host when omitted; None (noise source "device") = drawn on the
@@ -921,7 +968,14 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
         mask = mask[None].expand(B, *mask.shape)
     context = self._cond_stage_model(cond_model_inputs)
     z0 = self.get_latents(imgs, noise=encode_noise, seed=seed, first_sample_index=first_sample_index)
-    _, h, w, c = z0.shape
+    return self._sdedit(context, z0, k, guidance_scale, gsched, mask, q_noises, noises, seed, first_sample_index,
+                        record)
+
+  def _sdedit(self, context, z0, k, guidance_scale, gsched, mask, q_noises, noises, seed, first_sample_index, record):
+    """The img2img loop from the latents z0 [B,h,w,c] on: q_sample to the level of steps[k-1], DDIM indices k-1 .. 0
+    (with the blend when `mask` is given), decode."""
+    n = len(self._ddim_steps)
+    B, h, w, c = z0.shape
     if mask is not None and tuple(mask.shape) != (B, h, w):
       raise ValueError(f"mask must be [B,h,w] = {(B, h, w)} (or [h,w]) at latent resolution, "
                        f"got {tuple(mask.shape)}")
@@ -955,6 +1009,56 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
         ops.q_sample(z0_buf, q_buf[k - 1], t_start, sa, sb, self._xt, x_unet_out=self._x2)
 
     return self._denoise(k, set_start, guidance_scale, gsched, noise_table, masked, rng, record)
+
+  # ---- two-pass high-resolution sampling --------------------------------
+  def ddim_p_sample_loop_hires(self, cond_model_inputs, shape, hires_shape, strength=0.5, resize="bilinear",
+                               guidance_scale=5., x_T=None, noises=None, q_noises=None, seed=0, first_sample_index=0,
+                               record=None, guidance_interval=None):
+    """Two-pass sampling ("hires fix").  Pass 1 is ddim_p_sample_loop at `shape` [B,h,w,c], the
+    U-Net's training size, without the decode.  Its latents are resized to `hires_shape` [B,H,W,c] on the device
+    (ops.resize_nhwc; `resize` "nearest", "bilinear" or "bicubic").  Pass 2 is the unmasked img2img loop from those
+    latents z0, no encoder involved: k = int(strength * N), start from q_sample(z0, steps[k-1], Q[k-1]), DDIM indices
+    k-1 .. 0 at `hires_shape`, decode.  Every solver, step table, guidance schedule and noise source runs in both
+    passes; each shape keeps its own state and captured graph, so a second call captures nothing.
+    `x_T` [B,h,w,c] is pass 1's; `noises` (read when eta > 0) a pair (pass 1's [N,B,h,w,c], pass 2's [N,B,H,W,c]),
+    either may be None; `q_noises` [N,B,H,W,c] is pass 2's Q.  What is not given is drawn from `seed` in pass 1 and
+    from hires_seed(seed) in pass 2, so that no draw of one pass repeats a draw of the other.  `record` receives x
+    after each of the N + k steps (eager, no graph).  Returns the decoded images [B,fH,fW,3]; the final latents stay
+    in self._xt, a copy of pass 1's in self.hires_first_latents."""
+    shape, hires_shape = tuple(int(v) for v in shape), tuple(int(v) for v in hires_shape)
+    if len(shape) != 4 or len(hires_shape) != 4:
+      raise ValueError(f"shape {shape} and hires_shape {hires_shape} must both be [B,h,w,c]")
+    if (shape[0], shape[3]) != (hires_shape[0], hires_shape[3]):
+      raise ValueError(f"hires_shape {hires_shape} must keep the batch and channels of shape {shape}")
+    if resize not in RESIZE_MODES:
+      raise ValueError(f"resize must be one of {RESIZE_MODES}, got {resize!r}")
+    div = 1 << max(getattr(self._unet, "skip_lvl", (0,)))
+    if hires_shape[1] < 1 or hires_shape[2] < 1 or hires_shape[1] % div or hires_shape[2] % div:
+      raise ValueError(f"hires_shape {hires_shape}: the U-Net halves its input {div.bit_length() - 1} times, the "
+                       f"extents must be positive multiples of {div}")
+    n = len(self._ddim_steps)
+    k = img2img_start(strength, n)
+    noises1, noises2 = (None, None) if noises is None else noises
+    gsched = self._guidance(guidance_scale, guidance_interval)
+    context = self._cond_stage_model(cond_model_inputs)
+    first = self._sample_from(context, shape, n, guidance_scale, gsched, x_T, noises1, seed, first_sample_index,
+                              record, decode=False)
+    self.hires_first_latents = first.clone()   # (pass 2 reuses the buffer when both shapes are the same)
+    self._hires_events = (self._loop_events, None)
+    z0 = ops.resize_nhwc(first, hires_shape[1:3], resize)
+    images = self._sdedit(context, z0, k, guidance_scale, gsched, None, q_noises, noises2, hires_seed(seed),
+                          first_sample_index, record)
+    self._hires_events = (self._hires_events[0], self._loop_events)
+    return images
+
+  def last_hires_ms(self):
+    """(ms of pass 1's loop, ms of pass 2's loop) of the last ddim_p_sample_loop_hires call: device time, all steps of
+    each (synchronises)."""
+    out = []
+    for t0, t1, _ in self._hires_events:
+      t1.synchronize()
+      out.append(t0.elapsed_time(t1))
+    return tuple(out)
 
   def _init_images(self, init_images, B):
     """init_images [B,H,W,3] (or [H,W,3], tiled over the batch) as a contiguous float32 tensor."""

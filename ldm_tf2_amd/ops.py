@@ -21,7 +21,7 @@ __all__ = [
     "bmm_nt", "conv3x3_small", "groupnorm", "layernorm", "softmax_rows", "attention",
     "time_embedding", "gemv", "cfg_ddim_update", "cfg_ddim_update_masked", "cfg_plms_update", "q_sample",
     "philox_u32", "normal_fill", "q_sample_rng", "cfg_ddim_update_rng", "cfg_plms_update_rng", "cfg_ms_update",
-    "cfg_ms_update_rng", "cfg_sched_update", "cfg_ddim_invert_update", "window_gather", "window_fold", "post_quant", "vq_nearest", "embedding",
+    "cfg_ms_update_rng", "cfg_sched_update", "cfg_ddim_invert_update", "window_gather", "window_fold", "resize_nhwc", "post_quant", "vq_nearest", "embedding",
     "minmax_u8", "cast",
 ]
 
@@ -1070,6 +1070,26 @@ def window_fold(eps_win, eps_canvas, window, stride):
   check(lib.ldm_window_fold(_ptr(_f32(eps_win, "eps_win")), _ptr(_f32(eps_canvas, "eps_canvas")), halves, *dims,
                             _stream()), "ldm_window_fold")
   return eps_canvas
+
+
+def resize_nhwc(x, size, mode, out=None):
+  """Latent resize (include/ldm_hip.h): x [B,H,W,c] float32 -> [B,Ho,Wo,c] float32, `size` =
+  (Ho, Wo), `mode` "nearest", "bilinear" or "bicubic" (the align_corners=False rules, no antialiasing; an int is
+  handed to the launcher as it is).  `out`: where the result goes (contiguous; allocated when omitted)."""
+  if isinstance(mode, str):
+    if mode not in _lib.RESIZE_MODES:
+      raise ValueError(f"resize mode must be one of {tuple(_lib.RESIZE_MODES)}, got {mode!r}")
+    mode = _lib.RESIZE_MODES[mode]
+  assert x.dim() == 4 and x.is_contiguous(), (tuple(x.shape), x.stride())
+  B, H, W, c = (int(v) for v in x.shape)
+  Ho, Wo = (int(v) for v in size)
+  if out is None:
+    out = torch.empty(B, max(Ho, 0), max(Wo, 0), c, dtype=torch.float32, device=x.device)
+  elif Ho >= 1 and Wo >= 1:
+    assert out.is_contiguous() and tuple(out.shape) == (B, Ho, Wo, c), (tuple(out.shape), (B, Ho, Wo, c))
+  check(lib.ldm_resize_nhwc(_ptr(_f32(x, "x")), _ptr(_f32(out, "out")), B, H, W, c, Ho, Wo, int(mode), _stream()),
+        "ldm_resize_nhwc")
+  return out
 
 
 def post_quant(latents, scale_factor, kernel_io, bias, out):

@@ -49,6 +49,13 @@ inverted `int(strength * N)` DDIM steps under `source_prompt` (DDIM inversion, g
 default 1) and sampled back under `text_prompt`, the target, with `guidance_scale`.  The same
 prompt twice with both scales 1 reconstructs the image.  `mask`, `window` and `sample_save_progress` cannot be combined
 with it.  Without `source_prompt` nothing changes.
+
+Two-pass high resolution ("hires fix"): optional `ldm_sampling` keys `hires_shape: [B, H, W, c]`, `hires_strength`
+(default 0.5) and `hires_resize` (`nearest`, `bilinear` (default) or `bicubic`).  With `hires_shape`, `latent_shape` is
+sampled as usual, the latents are resized to `hires_shape` on the device and the last `int(hires_strength * N)` DDIM
+steps run again at that size from the re-noised latents; the images are decoded at
+`hires_shape`.  Every solver, step table, noise source and guidance schedule runs in both passes; `init_image`, `mask`,
+`window`, `source_prompt` and `sample_save_progress` cannot be combined with it.  Without `hires_shape` nothing changes.
 """
 from __future__ import annotations
 
@@ -62,7 +69,7 @@ import yaml
 
 from . import ops
 from .autoencoder import AutoencoderKL, AutoencoderVQ
-from .model_runners import LatentDiffusionModelSampler, latent_mask, window_and_stride
+from .model_runners import RESIZE_MODES, LatentDiffusionModelSampler, latent_mask, window_and_stride
 from .tokenizer import get_token_ids
 from .transformer import TransformerModel
 from .unet import UNet
@@ -99,7 +106,7 @@ def compvis_manifest_configs(config):
   if kind == "kl":
     ae_cfg = dict(config["autoencoder_kl"], attention_resolutions=())      # KL ignores it (autoencoder.py:339)
   else:
-    ae_cfg = dict(config["autoencoder_vq"], latent_size=config["ldm_sampling"]["latent_shape"][1])
+    ae_cfg = dict(config["autoencoder_vq"], latent_size=decode_latent_size(config))
   return dict(unet_cfg=unet_cfg, transformer_cfg=dict(config["cond_stage_model"]), autoencoder_cfg=ae_cfg)
 
 
@@ -162,6 +169,31 @@ def panorama_kwargs(config, seed):
   return dict(window=window, stride=stride, seed=seed)
 
 
+def hires_call(config, token_ids, seed):
+  """`ldm_sampling.hires_shape: [B, H, W, c]` with `hires_strength` / `hires_resize` (the
+  reference's YAML has no such keys): the two-pass loop's call.  The loop has no init image, mask, windows, source
+  prompt or progress frames."""
+  samp = config["ldm_sampling"]
+  for key in ("init_image", "mask", "window", "source_prompt", "sample_save_progress"):
+    if samp.get(key) is not None and samp.get(key) is not False:
+      raise ValueError(f"ldm_sampling.hires_shape cannot be combined with ldm_sampling.{key}")
+  hs = samp["hires_shape"]
+  if not isinstance(hs, (list, tuple)) or len(hs) != 4 or any(not isinstance(v, int) for v in hs):
+    raise ValueError(f"ldm_sampling.hires_shape must be [B, H, W, c] (ints), got {hs!r}")
+  resize = samp.get("hires_resize", "bilinear")
+  if resize not in RESIZE_MODES:
+    raise ValueError(f"ldm_sampling.hires_resize must be one of {RESIZE_MODES}, got {resize!r}")
+  kwargs = dict(strength=float(samp.get("hires_strength", 0.5)), resize=resize, guidance_scale=samp["guidance_scale"],
+                seed=seed, **guidance_kwargs(config))
+  return "ddim_p_sample_loop_hires", (token_ids, samp["latent_shape"], list(hs)), kwargs
+
+
+def decode_latent_size(config):
+  """The latent extent the autoencoder decodes at: `hires_shape`'s when the key is there, else `latent_shape`'s."""
+  samp = config["ldm_sampling"]
+  return (samp.get("hires_shape") or samp["latent_shape"])[1]
+
+
 def _init_images(samp):
   """`ldm_sampling.init_image`: a .npy of uint8 [H,W,3] or [B,H,W,3], read as x / 127.5 - 1."""
   img = np.load(samp["init_image"])
@@ -194,6 +226,8 @@ def sampling_call(config, token_ids, seed, source_ids=None):
   ids of `ldm_sampling.source_prompt` when the key is there."""
   samp = config["ldm_sampling"]
   base = (token_ids, samp["latent_shape"], samp["guidance_scale"])
+  if samp.get("hires_shape") is not None:
+    return hires_call(config, token_ids, seed)
   if samp.get("source_prompt") is not None:
     return edit_call(config, token_ids, source_ids, seed)
   if samp.get("window") is not None:
@@ -222,7 +256,7 @@ def build_from_config(config, dtype=torch.bfloat16, device="cuda:0", seed=2, use
   kind = config["ldm_sampling"]["autoencoder_type"]
   if kind not in ("kl", "vq"):
     raise NotImplementedError("invalid autoencoder type.")
-  latent_size = config["ldm_sampling"]["latent_shape"][1]
+  latent_size = decode_latent_size(config)
   hidden = config["cond_stage_model"]["hidden_size"]
   if ck.get("compvis"):
     # one CompVis PyTorch checkpoint for all three models (checkpoint.py; what the
