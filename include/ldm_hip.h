@@ -602,6 +602,26 @@ int ldm_window_fold(const float* eps_win, float* eps_canvas, int halves, int B, 
 #define LDM_RESIZE_BICUBIC 2
 int ldm_resize_nhwc(const float* x, float* out, int B, int H, int W, int c, int Ho, int Wo, int mode, void* stream);
 
+/*
+ * Antialiased resample: x [B][H][W][c] float32 -> out [B][Ho][Wo][c] float32 with a filter
+ * whose footprint grows with the shrink factor (the rule of PIL's Image.resize and of torch's antialias=True), in two
+ * launches: along W into tmp [B][H][Wo][c] float32 (scratch of the caller), then along H into out.  The caller hands
+ * in one table per axis (ldm_tf2_amd/resample.py builds them on the host in float64, rounded once to float32): for
+ * an axis of source extent L and output extent Lo, start int32 [Lo] and w float32 [Lo][taps]; output index i reads the
+ * source indices start[i] .. start[i] + taps - 1 with the weights w[i][0 .. taps).  Every row must lie inside [0, L):
+ * 0 <= start[i] <= L - taps; rows with fewer taps are zero-filled.  The kernels do not check the table's contents.
+ * Per output element acc = fma(w[i][j], x_j, acc) for ascending j from acc = 0, float32, the same chain in both
+ * paths below; taps == 1 (an identity table: every weight is 1) copies the source bits.  A thread owns an output
+ * element: no atomics, the result is deterministic.
+ *
+ * c % 4 == 0 with x, tmp and out 16-byte aligned moves one channel quad per thread in 16-byte accesses; any other
+ * c >= 1, or a pointer aligned to its element only, takes an element-wise path with the same bits.  LDM_ERR_ARG: a
+ * null pointer, an extent, B or c below 1, or taps below 1 or above the axis's source extent; nothing is launched.
+ */
+int ldm_resample_nhwc(const float* x, float* tmp, float* out, int B, int H, int W, int c, int Ho, int Wo,
+                      const int32_t* xstart, const float* xw, int xtaps, const int32_t* ystart, const float* yw,
+                      int ytaps, void* stream);
+
 /* decode_first_stage prologue (model_runners.py:426 + autoencoder.py:362,434):
  * out = Dense_{C->C}(latents / scale_factor), C <= 8; float32 in, out_dtype out. */
 int ldm_post_quant(const float* latents, float scale_factor, const float* kernel_io,

@@ -419,6 +419,7 @@ class AutoencoderVQ(_AutoencoderBase):
     self._latent_channels, self._channels, self._num_blocks = latent_channels, channels, num_blocks
     self._multipliers, self._vocab_size, self._beta = tuple(multipliers), vocab_size, beta
     self._attention_resolutions = tuple(attention_resolutions)
+    self._latent_size = latent_size              # (the one size its attention weights were laid out for)
     self._build(dict(latent_channels=latent_channels, channels=channels, num_blocks=num_blocks,
                      multipliers=self._multipliers, attention_resolutions=self._attention_resolutions,
                      latent_size=latent_size, vocab_size=vocab_size),

@@ -52,6 +52,10 @@ ddim_p_sample_loop_hires samples at the U-Net's training 
 (ldm_resize_nhwc) and re-runs the last int(strength * N) DDIM indices at the larger size, the unmasked img2img loop
 without an encoder.  The sampler keeps the device state and the captured graphs of every latent shape it has run
 (_alloc_state), so the two passes of a call, and later calls, replay two graphs captured once.
+
+image_size= / fit= / resample= on the image-driven loops, and pixel_filter= on the two-pass loop
+bring init images, pixel masks and pass 1's decoded image to the size the models need with the antialiased resample
+(ldm_resample_nhwc, tables from resample.py) on the device, next to the encoder.
 """
 from __future__ import annotations
 
@@ -63,6 +67,7 @@ import torch
 from . import ops
 from ._lib import LdmHipError
 from .autoencoder import AutoencoderKL, AutoencoderVQ
+from .resample import check_filter, crop_box
 
 
 def _tf_linspace_f32(start, stop, num):
@@ -101,6 +106,7 @@ XT_STREAM = 0                    # x_T
 ETA_STREAM = 1 << 29             # + i: eta noise of the step at DDIM index i
 NOISE_SOURCES = ("host", "device")
 RESIZE_MODES = ("nearest", "bilinear", "bicubic")
+FITS = ("stretch", "crop")       # image_size=: the whole source, or its centred box of the target's aspect ratio
 
 
 def hires_seed(seed):
@@ -180,6 +186,28 @@ def latent_mask(pixel_mask, f):
   B, H, W = m.shape
   keep = (m != 0).reshape(B, H // f, f, W // f, f).all(axis=(2, 4))
   return keep.astype(np.float32)
+
+
+def latent_mask_fit(pixel_mask, size):
+  """Pixel mask [B,Hs,Ws] (or [Hs,Ws]; nonzero = keep) of any extents -> float32 [B,h,w], `size` = (h, w) (DESIGN.md
+  section 15).  Latent cell y covers the source rows floor(y Hs / h) .. ceil((y + 1) Hs / h) - 1, every row any part
+  of which falls into the cell, in integer arithmetic; columns alike.  A cell is kept only if all the pixels it
+  covers are, so every pixel marked for regeneration is regenerated.  At Hs = f h, Ws = f w this is latent_mask."""
+  m = np.asarray(pixel_mask.cpu() if isinstance(pixel_mask, torch.Tensor) else pixel_mask)
+  if m.ndim == 2:
+    m = m[None]
+  h, w = (int(v) for v in size)
+  if m.ndim != 3 or min(m.shape[1:]) < 1 or h < 1 or w < 1:
+    raise ValueError(f"pixel mask of shape {m.shape} is not a non-empty [B,H,W], or the latent size {(h, w)} is empty")
+  B, Hs, Ws = m.shape
+  keep = m != 0
+  rows = np.empty((B, h, Ws), dtype=bool)
+  for y in range(h):
+    rows[:, y] = keep[:, (y * Hs) // h:-((-(y + 1) * Hs) // h)].all(axis=1)
+  out = np.empty((B, h, w), dtype=bool)
+  for x in range(w):
+    out[:, :, x] = rows[:, :, (x * Ws) // w:-((-(x + 1) * Ws) // w)].all(axis=2)
+  return out.astype(np.float32)
 
 
 def window_origins(L, l, s):
@@ -947,7 +975,8 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
 
   def ddim_p_sample_loop_img2img(self, cond_model_inputs, init_images, guidance_scale=5., strength=0.75,
                                  mask=None, encode_noise=None, q_noises=None, noises=None, seed=0,
-                                 first_sample_index=0, record=None, guidance_interval=None):
+                                 first_sample_index=0, record=None, guidance_interval=None, image_size=None,
+                                 fit="stretch", resample="lanczos3"):
     """img2img (SDEdit) and masked inpainting on the DDIM loop.
     cond_model_inputs: token ids [uncond x B; cond x B].  init_images [B,H,W,3] (or [H,W,3], tiled) float32
     in [-1, 1].  z0 = get_latents(init_images, encode_noise); k = int(strength * N); the loop starts from
@@ -956,16 +985,27 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     `q_noises` [N,B,h,w,c] (Q, indexed by DDIM index; else seed's Q_STREAM + i per global sample index),
     `noises` as in ddim_p_sample_loop, `record` receives x after each of the k steps (eager, no graph).
     `guidance_scale` / `guidance_interval` as in ddim_p_sample_loop (the table covers all N indices; the loop walks
-    its first k).  Returns the decoded images; the final latents stay in self._xt."""
+    its first k).  `image_size` = (H, W) (None: everything above, unchanged): init images of
+    any extents are brought to (H, W) on the device before the encoder -- `fit` "stretch" resamples the whole image,
+    "crop" its centred box of the target's aspect ratio (resample.crop_box), `resample` names the filter of
+    ops.resample_nhwc; images already (H, W) take the path above untouched -- and `mask` may also be a pixel mask at the
+    source images' size ([B,Hs,Ws] or [Hs,Ws], nonzero = keep), reduced over the same box by latent_mask_fit; a mask
+    whose extents are the latent ones is read as a latent mask.  Returns the decoded images; the final latents stay
+    in self._xt."""
+    size = self._image_size(image_size, fit, resample)
     gsched = self._guidance(guidance_scale, guidance_interval)
     n = len(self._ddim_steps)
     k = img2img_start(strength, n)
     B = len(cond_model_inputs) // 2
     imgs = self._init_images(init_images, B)
+    if mask is not None and size is not None:
+      mask = self._fit_mask(mask, tuple(imgs.shape[1:3]), size, fit)
     if mask is not None:
       mask = torch.as_tensor(np.asarray(mask) if not isinstance(mask, torch.Tensor) else mask, dtype=torch.float32)
       if mask.dim() == 2:
         mask = mask[None].expand(B, *mask.shape)
+    if size is not None:
+      imgs = self._fit_images(imgs, size, fit, resample)
     context = self._cond_stage_model(cond_model_inputs)
     z0 = self.get_latents(imgs, noise=encode_noise, seed=seed, first_sample_index=first_sample_index)
     return self._sdedit(context, z0, k, guidance_scale, gsched, mask, q_noises, noises, seed, first_sample_index,
@@ -1013,7 +1053,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
   # ---- two-pass high-resolution sampling --------------------------------
   def ddim_p_sample_loop_hires(self, cond_model_inputs, shape, hires_shape, strength=0.5, resize="bilinear",
                                guidance_scale=5., x_T=None, noises=None, q_noises=None, seed=0, first_sample_index=0,
-                               record=None, guidance_interval=None):
+                               record=None, guidance_interval=None, pixel_filter=None, encode_noise=None):
     """Two-pass sampling ("hires fix").  Pass 1 is ddim_p_sample_loop at `shape` [B,h,w,c], the
     U-Net's training size, without the decode.  Its latents are resized to `hires_shape` [B,H,W,c] on the device
     (ops.resize_nhwc; `resize` "nearest", "bilinear" or "bicubic").  Pass 2 is the unmasked img2img loop from those
@@ -1024,7 +1064,12 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     either may be None; `q_noises` [N,B,H,W,c] is pass 2's Q.  What is not given is drawn from `seed` in pass 1 and
     from hires_seed(seed) in pass 2, so that no draw of one pass repeats a draw of the other.  `record` receives x
     after each of the N + k steps (eager, no graph).  Returns the decoded images [B,fH,fW,3]; the final latents stay
-    in self._xt, a copy of pass 1's in self.hires_first_latents."""
+    in self._xt, a copy of pass 1's in self.hires_first_latents.
+    `pixel_filter` "triangle", "cubic" or "lanczos3" (None: everything above, unchanged)
+    enlarges in pixel space instead: pass 1's latents are decoded to the decoder's float image, the image is
+    resampled to f times the extents of `hires_shape` (ops.resample_nhwc) and encoded again (get_latents with
+    `encode_noise` [B,H,W,c], else drawn from hires_seed(seed)'s ENCODE_STREAM); those latents are pass 2's z0 and
+    `resize` is not used.  Needs an autoencoder with its encoder that decodes at both sizes."""
     shape, hires_shape = tuple(int(v) for v in shape), tuple(int(v) for v in hires_shape)
     if len(shape) != 4 or len(hires_shape) != 4:
       raise ValueError(f"shape {shape} and hires_shape {hires_shape} must both be [B,h,w,c]")
@@ -1036,6 +1081,17 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     if hires_shape[1] < 1 or hires_shape[2] < 1 or hires_shape[1] % div or hires_shape[2] % div:
       raise ValueError(f"hires_shape {hires_shape}: the U-Net halves its input {div.bit_length() - 1} times, the "
                        f"extents must be positive multiples of {div}")
+    if pixel_filter is not None:
+      check_filter(pixel_filter, "pixel_filter")
+      if getattr(self._autoencoder, "_encoder", None) is None:
+        raise ValueError("pixel_filter encodes the resampled image: the autoencoder was built without its encoder "
+                         "(pass with_encoder=True)")
+      bound = getattr(self._autoencoder, "_latent_size", None)
+      if bound is not None and shape[1:3] != hires_shape[1:3]:
+        raise ValueError(f"pixel_filter decodes at {shape[1:3]} and at {hires_shape[1:3]}: this autoencoder was built "
+                         f"for the one latent size {bound}")
+    elif encode_noise is not None:
+      raise ValueError("encode_noise is the noise of pixel_filter's encode: it cannot be given without pixel_filter")
     n = len(self._ddim_steps)
     k = img2img_start(strength, n)
     noises1, noises2 = (None, None) if noises is None else noises
@@ -1045,7 +1101,13 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
                               record, decode=False)
     self.hires_first_latents = first.clone()   # (pass 2 reuses the buffer when both shapes are the same)
     self._hires_events = (self._loop_events, None)
-    z0 = ops.resize_nhwc(first, hires_shape[1:3], resize)
+    if pixel_filter is None:
+      z0 = ops.resize_nhwc(first, hires_shape[1:3], resize)
+    else:
+      image = self.decode_first_stage(first)   # (the decoder's float image: no min-max, no uint8)
+      f = image.shape[1] // shape[1]
+      image = ops.resample_nhwc(image, (f * hires_shape[1], f * hires_shape[2]), pixel_filter)
+      z0 = self.get_latents(image, noise=encode_noise, seed=hires_seed(seed), first_sample_index=first_sample_index)
     images = self._sdedit(context, z0, k, guidance_scale, gsched, None, q_noises, noises2, hires_seed(seed),
                           first_sample_index, record)
     self._hires_events = (self._hires_events[0], self._loop_events)
@@ -1069,6 +1131,62 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     if imgs.dim() != 4 or imgs.shape[0] != B or imgs.shape[-1] != 3:
       raise ValueError(f"init_images must be [B={B},H,W,3] or [H,W,3], got {tuple(imgs.shape)}")
     return imgs.contiguous()
+
+  # ---- init images and masks of any size ------------------------------
+  def _pixel_factor(self):
+    """Image pixels per latent cell along an axis: the autoencoder halves len(multipliers) - 1 times (1 for an
+    autoencoder that does not say)."""
+    mult = getattr(self._autoencoder, "_multipliers", None)
+    return 1 if mult is None else 2 ** (len(mult) - 1)
+
+  def _image_size(self, image_size, fit, resample):
+    """The checked `image_size` keyword as (H, W), None when it was not given.  Raises before anything is allocated:
+    an unknown `fit` or filter, or extents that are not positive multiples of f * 2^levels (f the autoencoder's
+    pixels per latent cell, levels the U-Net's halvings)."""
+    if image_size is None:
+      return None
+    if fit not in FITS:
+      raise ValueError(f"fit must be one of {FITS}, got {fit!r}")
+    check_filter(resample, "resample")
+    if np.ndim(image_size) != 1 or len(image_size) != 2 or any(int(v) != v for v in image_size):
+      raise ValueError(f"image_size must be (H, W) in pixels, got {image_size!r}")
+    H, W = (int(v) for v in image_size)
+    f, div = self._pixel_factor(), 1 << max(getattr(self._unet, "skip_lvl", (0,)))
+    if H < 1 or W < 1 or H % (f * div) or W % (f * div):
+      raise ValueError(f"image_size {(H, W)}: the autoencoder maps {f} pixels to a latent cell and the U-Net halves "
+                       f"its input {div.bit_length() - 1} times, the extents must be positive multiples of {f * div}")
+    return H, W
+
+  def _fit_images(self, imgs, size, fit, resample):
+    """init images [B,Hs,Ws,3] -> [B,H,W,3] on the device: the crop box (`fit` "crop"), then ops.resample_nhwc.
+    Images that already are (H, W) come back as they are (the host tensor: the encoder's path of today)."""
+    src = tuple(int(v) for v in imgs.shape[1:3])
+    if src == tuple(size):
+      return imgs
+    x = imgs.to(self.device)
+    if fit == "crop":
+      y0, x0, hc, wc = crop_box(src, size)
+      x = x[:, y0:y0 + hc, x0:x0 + wc]
+    return ops.resample_nhwc(x.contiguous(), size, resample)
+
+  def _fit_mask(self, mask, src, size, fit):
+    """`mask` with image_size=: a latent mask ([B,h,w] or [h,w], (h, w) = size / f) is returned as given; a pixel
+    mask at the source images' extents `src` becomes the latent mask of the same box the images keep
+    (latent_mask_fit); any other shape is a ValueError."""
+    f = self._pixel_factor()
+    h, w = size[0] // f, size[1] // f
+    shape = tuple(int(v) for v in np.shape(mask))
+    if len(shape) in (2, 3) and shape[-2:] == (h, w):
+      return mask
+    if len(shape) not in (2, 3) or shape[-2:] != tuple(src):
+      raise ValueError(f"mask of shape {shape} is neither a latent mask [B,{h},{w}] (or [{h},{w}]) nor a pixel mask "
+                       f"at the init images' size [B,{src[0]},{src[1]}] (or [{src[0]},{src[1]}])")
+    m = np.asarray(mask.cpu() if isinstance(mask, torch.Tensor) else mask)
+    if fit == "crop" and tuple(src) != tuple(size):
+      y0, x0, hc, wc = crop_box(src, size)
+      m = m[..., y0:y0 + hc, x0:x0 + wc]
+    lm = latent_mask_fit(m, (h, w))
+    return lm[0] if len(shape) == 2 else lm
 
   # ---- DDIM inversion (DESIGN.md section 13) ---------------------------------------------------
   def inversion_timesteps(self):
@@ -1119,7 +1237,8 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
                                pred_x0_out=pred_x0_out)
 
   def ddim_invert_loop(self, cond_model_inputs, init_images=None, latents=None, guidance_scale=1., strength=1.,
-                       encode_noise=None, seed=0, first_sample_index=0, record=None):
+                       encode_noise=None, seed=0, first_sample_index=0, record=None, image_size=None,
+                       fit="stretch", resample="lanczos3"):
     """DDIM inversion: the deterministic, first-order DDIM ODE run upwards from z0, whatever
     sampler= and eta the sampler was built with.  cond_model_inputs: token ids [uncond x B; cond x B].  Exactly one
     of `init_images` ([B,H,W,3] or [H,W,3], tiled; float32 in [-1, 1]; z0 = get_latents(init_images, encode_noise))
@@ -1127,7 +1246,11 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     indices 0 .. k-1: e = eps(x, t_in[i]) with the guidance scale (1: the conditional eps alone), x0 = (x -
     sqrt(1 - a_prev[i]) e) / sqrt(a_prev[i]), x <- (x0 + c2[i] e) / c1[i].  `record` receives x after each step
     (eager, no graph).  Returns the latents on the level of steps[k-1], float32 [B,h,w,c] on the device (a copy;
-    they also stay in self._xt): ddim_p_sample_loop(x_T=, start_index=k) maps them back."""
+    they also stay in self._xt): ddim_p_sample_loop(x_T=, start_index=k) maps them back.  `image_size` / `fit` /
+    `resample` as in ddim_p_sample_loop_img2img, with `init_images` only."""
+    size = self._image_size(image_size, fit, resample)
+    if size is not None and init_images is None:
+      raise ValueError("image_size resamples init_images: it cannot be given with latents")
     if np.ndim(guidance_scale) > 0:
       raise ValueError("the inversion loop takes one float guidance_scale: a guidance schedule is not supported")
     if (init_images is None) == (latents is None):
@@ -1137,8 +1260,10 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     B = len(cond_model_inputs) // 2
     context = self._cond_stage_model(cond_model_inputs)
     if latents is None:
-      z0 = self.get_latents(self._init_images(init_images, B), noise=encode_noise, seed=seed,
-                            first_sample_index=first_sample_index)
+      imgs = self._init_images(init_images, B)
+      if size is not None:
+        imgs = self._fit_images(imgs, size, fit, resample)
+      z0 = self.get_latents(imgs, noise=encode_noise, seed=seed, first_sample_index=first_sample_index)
     else:
       z0 = torch.as_tensor(np.asarray(latents) if not isinstance(latents, torch.Tensor) else latents,
                            dtype=torch.float32)
@@ -1165,20 +1290,24 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
 
   def ddim_p_sample_loop_edit(self, source_inputs, target_inputs, init_images, guidance_scale=5., strength=0.75,
                               invert_guidance_scale=1., encode_noise=None, noises=None, seed=0, first_sample_index=0,
-                              record=None, guidance_interval=None):
+                              record=None, guidance_interval=None, image_size=None, fit="stretch",
+                              resample="lanczos3"):
     """Prompt editing of a real image: z0 = get_latents(init_images); k = int(strength * N)
     inversion steps under the source prompt (`source_inputs`, scale `invert_guidance_scale`); then DDIM indices
     k-1 .. 0 of the configured solver under the target prompt (`target_inputs`, `guidance_scale` /
     `guidance_interval` as in ddim_p_sample_loop).  Both id arrays are [uncond x B; cond x B].  With the same ids and
-    both scales 1 this reconstructs the image.  `record` receives x after each sampling step.  Returns the decoded
-    images; the final latents stay in self._xt."""
+    both scales 1 this reconstructs the image.  `record` receives x after each sampling step.  `image_size` / `fit` /
+    `resample` as in ddim_p_sample_loop_img2img.  Returns the decoded images; the final latents
+    stay in self._xt."""
+    self._image_size(image_size, fit, resample)
     if np.shape(source_inputs) != np.shape(target_inputs):
       raise ValueError(f"source_inputs {np.shape(source_inputs)} and target_inputs {np.shape(target_inputs)} must "
                        "have the same shape")
     k = img2img_start(strength, len(self._ddim_steps))
     x = self.ddim_invert_loop(source_inputs, init_images=init_images, guidance_scale=invert_guidance_scale,
                               strength=strength, encode_noise=encode_noise, seed=seed,
-                              first_sample_index=first_sample_index)
+                              first_sample_index=first_sample_index, image_size=image_size, fit=fit,
+                              resample=resample)
     return self.ddim_p_sample_loop(target_inputs, tuple(x.shape), guidance_scale, x_T=x, noises=noises, seed=seed,
                                    first_sample_index=first_sample_index, record=record,
                                    guidance_interval=guidance_interval, start_index=k)

@@ -21,7 +21,7 @@ __all__ = [
     "bmm_nt", "conv3x3_small", "groupnorm", "layernorm", "softmax_rows", "attention",
     "time_embedding", "gemv", "cfg_ddim_update", "cfg_ddim_update_masked", "cfg_plms_update", "q_sample",
     "philox_u32", "normal_fill", "q_sample_rng", "cfg_ddim_update_rng", "cfg_plms_update_rng", "cfg_ms_update",
-    "cfg_ms_update_rng", "cfg_sched_update", "cfg_ddim_invert_update", "window_gather", "window_fold", "resize_nhwc", "post_quant", "vq_nearest", "embedding",
+    "cfg_ms_update_rng", "cfg_sched_update", "cfg_ddim_invert_update", "window_gather", "window_fold", "resize_nhwc", "resample_nhwc", "post_quant", "vq_nearest", "embedding",
     "minmax_u8", "cast",
 ]
 
@@ -1089,6 +1089,31 @@ def resize_nhwc(x, size, mode, out=None):
     assert out.is_contiguous() and tuple(out.shape) == (B, Ho, Wo, c), (tuple(out.shape), (B, Ho, Wo, c))
   check(lib.ldm_resize_nhwc(_ptr(_f32(x, "x")), _ptr(_f32(out, "out")), B, H, W, c, Ho, Wo, int(mode), _stream()),
         "ldm_resize_nhwc")
+  return out
+
+
+def resample_nhwc(x, size, filter="lanczos3", out=None):
+  """Antialiased resample (include/ldm_hip.h): x [B,H,W,c] float32 -> [B,Ho,Wo,c] float32, `size`
+  = (Ho, Wo), `filter` "triangle", "cubic" or "lanczos3".  The per-axis tables come from resample.device_taps (built
+  on the host on first use, cached per extents, filter and device); the W pass's result goes through a scratch
+  tensor of this call.  `out`: where the result goes (contiguous; allocated when omitted)."""
+  from . import resample as R
+  R.check_filter(filter, "resample filter")
+  assert x.dim() == 4 and x.is_contiguous(), (tuple(x.shape), x.stride())
+  B, H, W, c = (int(v) for v in x.shape)
+  Ho, Wo = (int(v) for v in size)
+  if Ho < 1 or Wo < 1:
+    raise ValueError(f"resample size must be positive, got {(Ho, Wo)}")
+  if out is None:
+    out = torch.empty(B, Ho, Wo, c, dtype=torch.float32, device=x.device)
+  else:
+    assert out.is_contiguous() and tuple(out.shape) == (B, Ho, Wo, c), (tuple(out.shape), (B, Ho, Wo, c))
+  _ptr(x)                                        # (a host tensor is refused before any table is built)
+  xs, xw, xt = R.device_taps(W, Wo, filter, x.device)
+  ys, yw, yt = R.device_taps(H, Ho, filter, x.device)
+  tmp = torch.empty(B, H, Wo, c, dtype=torch.float32, device=x.device)
+  check(lib.ldm_resample_nhwc(_ptr(_f32(x, "x")), _ptr(tmp), _ptr(_f32(out, "out")), B, H, W, c, Ho, Wo, _ptr(xs),
+                              _ptr(xw), xt, _ptr(ys), _ptr(yw), yt, _stream()), "ldm_resample_nhwc")
   return out
 
 

@@ -56,6 +56,14 @@ sampled as usual, the latents are resized to `hires_shape` on the device and the
 steps run again at that size from the re-noised latents; the images are decoded at
 `hires_shape`.  Every solver, step table, noise source and guidance schedule runs in both passes; `init_image`, `mask`,
 `window`, `source_prompt` and `sample_save_progress` cannot be combined with it.  Without `hires_shape` nothing changes.
+
+Init images and masks of any size: optional `ldm_sampling` keys `init_fit`, `exact` (default:
+`init_image` must already have f times the extents of `latent_shape`, as above), `stretch` (the whole image is resampled to
+that size on the device) or `crop` (its centred box of that aspect ratio is), and `init_filter`, `triangle`, `cubic` or
+`lanczos3` (default), the antialiased filter.  With `stretch` or `crop`, `mask` may be a pixel mask at the init image's
+own size.  Optional key `hires_pixel_filter` (the same three names; needs `hires_shape`): the two-pass loop enlarges
+in pixel space -- decode, resample, encode -- instead of resizing the latents, and the autoencoder is built with its
+encoder.  Without these keys nothing changes.
 """
 from __future__ import annotations
 
@@ -69,7 +77,8 @@ import yaml
 
 from . import ops
 from .autoencoder import AutoencoderKL, AutoencoderVQ
-from .model_runners import RESIZE_MODES, LatentDiffusionModelSampler, latent_mask, window_and_stride
+from ._lib import RESAMPLE_FILTERS
+from .model_runners import FITS, RESIZE_MODES, LatentDiffusionModelSampler, latent_mask, window_and_stride
 from .tokenizer import get_token_ids
 from .transformer import TransformerModel
 from .unet import UNet
@@ -111,8 +120,32 @@ def compvis_manifest_configs(config):
 
 
 def needs_encoder(config):
-  """img2img (`ldm_sampling.init_image`) encodes its init image: the autoencoder is built with its encoder."""
-  return bool(config["ldm_sampling"].get("init_image"))
+  """img2img (`ldm_sampling.init_image`) encodes its init image, and the two-pass loop with
+  `ldm_sampling.hires_pixel_filter` its resampled first pass: the autoencoder is built with its encoder."""
+  samp = config["ldm_sampling"]
+  return bool(samp.get("init_image")) or samp.get("hires_pixel_filter") is not None
+
+
+def _filter_name(samp, key, default=None):
+  name = samp.get(key, default)
+  if name is not None and name not in RESAMPLE_FILTERS:
+    raise ValueError(f"ldm_sampling.{key} must be one of {RESAMPLE_FILTERS}, got {name!r}")
+  return name
+
+
+def init_fit_kwargs(config):
+  """`ldm_sampling.init_fit` / `init_filter` (the reference's YAML has no such keys) as the
+  image-driven loops' keywords: nothing for `exact` (default), else the target size f * `latent_shape`'s extents,
+  the fit and the filter."""
+  samp = config["ldm_sampling"]
+  fit = samp.get("init_fit", "exact")
+  if fit not in ("exact",) + FITS:
+    raise ValueError(f"ldm_sampling.init_fit must be one of {('exact',) + FITS}, got {fit!r}")
+  resample = _filter_name(samp, "init_filter", "lanczos3")
+  if fit == "exact":
+    return {}
+  f = downsampling_factor(config)
+  return dict(image_size=(f * samp["latent_shape"][1], f * samp["latent_shape"][2]), fit=fit, resample=resample)
 
 
 def downsampling_factor(config):
@@ -185,6 +218,8 @@ def hires_call(config, token_ids, seed):
     raise ValueError(f"ldm_sampling.hires_resize must be one of {RESIZE_MODES}, got {resize!r}")
   kwargs = dict(strength=float(samp.get("hires_strength", 0.5)), resize=resize, guidance_scale=samp["guidance_scale"],
                 seed=seed, **guidance_kwargs(config))
+  if _filter_name(samp, "hires_pixel_filter") is not None:
+    kwargs["pixel_filter"] = samp["hires_pixel_filter"]
   return "ddim_p_sample_loop_hires", (token_ids, samp["latent_shape"], list(hs)), kwargs
 
 
@@ -217,7 +252,7 @@ def edit_call(config, token_ids, source_ids, seed):
     raise ValueError("ldm_sampling.source_prompt is set: its token ids are needed")
   kwargs = dict(strength=float(samp.get("strength", 0.75)),
                 invert_guidance_scale=float(samp.get("invert_guidance_scale", 1.)), seed=seed,
-                **guidance_kwargs(config))
+                **guidance_kwargs(config), **init_fit_kwargs(config))
   return "ddim_p_sample_loop_edit", (source_ids, token_ids, _init_images(samp), samp["guidance_scale"]), kwargs
 
 
@@ -226,8 +261,11 @@ def sampling_call(config, token_ids, seed, source_ids=None):
   ids of `ldm_sampling.source_prompt` when the key is there."""
   samp = config["ldm_sampling"]
   base = (token_ids, samp["latent_shape"], samp["guidance_scale"])
+  init_fit_kwargs(config)                        # (ValueError: an unknown init_fit or init_filter, whatever the loop)
   if samp.get("hires_shape") is not None:
     return hires_call(config, token_ids, seed)
+  if samp.get("hires_pixel_filter") is not None:
+    raise ValueError("ldm_sampling.hires_pixel_filter needs ldm_sampling.hires_shape")
   if samp.get("source_prompt") is not None:
     return edit_call(config, token_ids, source_ids, seed)
   if samp.get("window") is not None:
@@ -238,11 +276,15 @@ def sampling_call(config, token_ids, seed, source_ids=None):
     if samp.get("sample_save_progress"):
       raise ValueError("sample_save_progress is not supported with init_image")
     images = _init_images(samp)
-    kwargs = dict(strength=float(samp.get("strength", 0.75)), seed=seed, **guidance_kwargs(config))
+    fit = init_fit_kwargs(config)
+    kwargs = dict(strength=float(samp.get("strength", 0.75)), seed=seed, **guidance_kwargs(config), **fit)
     if samp.get("mask") is not None:
       pm = np.load(samp["mask"])
-      lm = latent_mask(pm, downsampling_factor(config))
-      kwargs["mask"] = lm[0] if pm.ndim == 2 else lm          # [h,w]: one mask, tiled over the batch
+      if fit:
+        kwargs["mask"] = pm                                     # (at the init image's size: the loop fits it)
+      else:
+        lm = latent_mask(pm, downsampling_factor(config))
+        kwargs["mask"] = lm[0] if pm.ndim == 2 else lm          # [h,w]: one mask, tiled over the batch
     return "ddim_p_sample_loop_img2img", (token_ids, images, samp["guidance_scale"]), kwargs
   if samp.get("sample_save_progress"):
     return "ddim_p_sample_loop_progressive", base, dict(seed=seed, **guidance_kwargs(config))
