@@ -580,6 +580,39 @@ int ldm_window_fold(const float* eps_win, float* eps_canvas, int halves, int B, 
                     int sy, int sx, void* stream);
 
 /*
+ * Seamless panoramas: the pair above with a wrap flag per axis (0 or 1) and a weighted fold.
+ * An unwrapped axis is the grid above.  A wrapped axis of extent L with window l and stride s has
+ *   n = ceil(L / s),  origin_i = i * s    (no clamp),
+ * and window i covers the cells (origin_i + j) mod L, j = 0 .. l - 1: the windows near the end cross the edge and
+ * come back on the other side.  Window order stays k = ky * nX + kx.
+ *
+ * ldm_window_gather_ex: ldm_window_gather with the source row and column taken modulo the extent on a wrapped axis;
+ * with both flags 0 the same bits as ldm_window_gather.
+ *
+ * ldm_window_fold_ex: wy [h] and wx [w] are float32 device tables of positive window-profile weights, the window
+ * element (jy, jx) weighing ww = wy[jy] * wx[jx].  Per canvas element, over the covering windows in ascending k and
+ * starting from the first covering term: num += ww * v, den += ww, out = num / den -- every product, sum and the
+ * division a float32 operation rounded once, nothing fused; no atomics.  Both tables NULL: uniform weights, the sum
+ * of the values over the count (ldm_window_fold's arithmetic and, when no axis wraps, its bits); a table of ones gives
+ * the bits of NULL.  One NULL and one non-NULL table is an error.  On a wrapped axis the windows covering position p
+ * are the i with i s <= p < i s + l followed by the i < n with p + L < i s + l.
+ *
+ * Paths and rejections as ldm_window_gather / ldm_window_fold; also LDM_ERR_ARG: a wrap flag that is not 0 or 1.
+ */
+int ldm_window_gather_ex(const float* canvas, void* x_win, int x_dtype, int B, int H, int W, int c, int h, int w,
+                         int sy, int sx, int wrap_y, int wrap_x, void* stream);
+int ldm_window_fold_ex(const float* eps_win, float* eps_canvas, int halves, int B, int H, int W, int c, int h, int w,
+                       int sy, int sx, int wrap_y, int wrap_x, const float* wy, const float* wx, void* stream);
+
+/*
+ * Circular padding for the wrapped decode: x [B][H][W][c] float32 -> out [B][H + 2 py]
+ * [W + 2 px][c] float32, out[b][y][x][:] = x[b][(y - py) mod H][(x - px) mod W][:].  0 <= py <= H, 0 <= px <= W
+ * (else LDM_ERR_ARG, as a null pointer or an extent, B or c below 1); py = px = 0 copies.  The two paths of the
+ * entries above (channel quads when c % 4 == 0 and both pointers are 16-byte aligned, else element-wise).
+ */
+int ldm_wrap_pad_nhwc(const float* x, float* out, int B, int H, int W, int c, int py, int px, void* stream);
+
+/*
  * Latent resize: x [B][H][W][c] float32 -> out [B][Ho][Wo][c] float32, enlarging or shrinking,
  * no antialiasing.  Per axis, with source extent L, output extent Lo and output index i:
  *   LDM_RESIZE_NEAREST:  the source index min((i * L) / Lo, L - 1) in integer arithmetic (i / 2 at 2x); the output is

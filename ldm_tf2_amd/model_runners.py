@@ -42,6 +42,9 @@ ddim_p_sample_loop_panorama samples a canvas wider than t
 crops the canvas into overlapping training-size windows (ldm_window_gather), runs the U-Net on the window rows,
 averages the windows' eps back onto the canvas (ldm_window_fold) and runs the configured solver's one update launch
 on the canvas.  The updates are affine in eps, so that equals averaging the windows' step outputs (MultiDiffusion).
+With `wrap` the windows of an axis cross the edge and come back on the other side, with `window_weights` the average
+is weighted by a window profile (ldm_window_gather_ex, ldm_window_fold_ex), and `wrap_decode_margin` decodes the canvas
+behind a circular margin (ldm_wrap_pad_nhwc) that is cropped from the images.
 
 ddim_invert_loop runs the deterministic DDIM step upwards from the latents of an image: a U-Net
 evaluation at the level the input is on and one update launch (ldm_cfg_ddim_invert_update) per step, replayed from a
@@ -221,6 +224,71 @@ def window_origins(L, l, s):
     raise ValueError(f"window stride {s} must lie in [1, {l}] (the window extent): windows leave no gaps")
   n = -((l - L) // s) + 1
   return [min(i * s, L - l) for i in range(n)]
+
+
+def wrap_origins(L, l, s):
+  """Origins of the windows along a wrapped axis: n = ceil(L / s) windows at origin_i = i * s,
+  no clamp; window i covers the cells (origin_i + j) mod L, j = 0 .. l - 1.  Needs 1 <= l <= L and 1 <= s <= l, as
+  window_origins; the origins are distinct and below L, every cell is covered, and a window covers a cell once."""
+  L, l, s = int(L), int(l), int(s)
+  if not 1 <= l <= L:
+    raise ValueError(f"window extent {l} must lie in [1, {L}] (the canvas extent)")
+  if not 1 <= s <= l:
+    raise ValueError(f"window stride {s} must lie in [1, {l}] (the window extent): windows leave no gaps")
+  return [i * s for i in range(-(-L // s))]
+
+
+WINDOW_WEIGHTS = ("uniform", "tent", "gaussian")
+
+
+def window_profile(kind, l):
+  """float32 [l]: the window profile `kind` along an axis of window extent l (DESIGN.md section 16).  "uniform": ones;
+  "tent": min(j + 1, l - j); "gaussian": exp(-(j - (l - 1) / 2)^2 / (2 (l / 4)^2)), computed in float64 and rounded.
+  All positive and symmetric."""
+  l = int(l)
+  if l < 1:
+    raise ValueError(f"window extent {l} must be at least 1")
+  j = np.arange(l, dtype=np.float64)
+  if kind == "uniform":
+    p = np.ones(l)
+  elif kind == "tent":
+    p = np.minimum(j + 1, l - j)
+  elif kind == "gaussian":
+    p = np.exp(-(j - (l - 1) / 2.) ** 2 / (2. * (l / 4.) ** 2))
+  else:
+    raise ValueError(f"window_weights must be one of {WINDOW_WEIGHTS} or a pair of arrays (wy, wx), got {kind!r}")
+  return p.astype(np.float32)
+
+
+def window_weight_tables(window_weights, window):
+  """(identity, tables) of the panorama loop's `window_weights` for `window` = (h, w): ("uniform", None) -- no
+  tables, the plain mean -- or (name or "tables", (wy float32 [h], wx float32 [w])) for "tent", "gaussian" or a pair
+  of positive finite arrays."""
+  h, w = window
+  if isinstance(window_weights, str):
+    if window_weights == "uniform":
+      return "uniform", None
+    return window_weights, (window_profile(window_weights, h), window_profile(window_weights, w))
+  if isinstance(window_weights, torch.Tensor) or not hasattr(window_weights, "__len__") or len(window_weights) != 2:
+    raise ValueError(f"window_weights must be one of {WINDOW_WEIGHTS} or a pair of arrays (wy, wx)")
+  tables = []
+  for t, n, what in zip(window_weights, (h, w), ("wy", "wx")):
+    t = np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t, dtype=np.float64)
+    if t.shape != (n,):
+      raise ValueError(f"window_weights: {what} has shape {t.shape}, expected {(n,)}")
+    with np.errstate(over="ignore"):
+      t = t.astype(np.float32)
+    if not (np.isfinite(t).all() and (t > 0).all()):
+      raise ValueError(f"window_weights: {what} must be positive and finite in float32")
+    tables.append(t)
+  return "tables", tuple(tables)
+
+
+def wrap_pair(wrap):
+  """`wrap` = (wrap_y, wrap_x) of a panorama call as a pair of bools."""
+  if np.ndim(wrap) != 1 or len(wrap) != 2 or any(not isinstance(v, (bool, np.bool_)) for v in wrap):
+    raise ValueError(f"wrap must be a pair of bools (wrap_y, wrap_x), got {wrap!r}")
+  return bool(wrap[0]), bool(wrap[1])
 
 
 def window_and_stride(window, stride=None):
@@ -547,7 +615,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
   # wait in _states, so a sampler that alternates between two shapes allocates and captures each
   # once.  What the graphs of every shape read alike (_rng, _gtab, the tables, the device counter) is not listed.
   _SHAPE_BUFFERS = ("_xt", "_x2", "_eps", "_ring", "_start", "_noise_buf", "_q_buf", "_z0_buf", "_mask_buf", "_t_buf",
-                    "_x_win", "_eps_win", "_win_key")
+                    "_x_win", "_eps_win", "_win_key", "_win_wy", "_win_wx")
   _SHAPE_GRAPHS = ("_graph", "_graph_key", "_sched_graphs", "_sched_key", "_inv_graph", "_inv_graph_key")
 
   def _alloc_state(self, B, h, w, c):
@@ -1324,36 +1392,78 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       self._win_key = key
       self._drop_graphs()
 
-  def _step_panorama(self, guidance_scale, noise_table, dec_index, window, stride, rng=False):
+  def _step_panorama(self, guidance_scale, noise_table, dec_index, window, stride, rng=False, wrap=(False, False),
+                     weights=None):
     """gather(canvas) -> unet(window rows) -> fold(eps) -> the solver's update on the canvas.  The update writes no
-    U-Net input: the next step's gather reads the canvas."""
+    U-Net input: the next step's gather reads the canvas.  A wrapped axis or `weights` = (wy, wx) device tables
+     makes the gather and the fold the _ex pair; otherwise the calls are section 12's."""
     B, H, W, c = self._xt.shape
-    ops.window_gather(self._xt, self._x_win, window, stride)
+    ex = any(wrap) or weights is not None
+    if ex:
+      ops.window_gather_ex(self._xt, self._x_win, window, stride, wrap)
+    else:
+      ops.window_gather(self._xt, self._x_win, window, stride)
     self._unet.forward(self._x_win, steps=self._steps_dev, index=self._index_dev, out=self._eps_win, paired_rows=True,
                        **self._temb_kwargs(dec_index))
-    ops.window_fold(self._eps_win, self._eps.view(2, B, H, W, c), window, stride)
+    if ex:
+      ops.window_fold_ex(self._eps_win, self._eps.view(2, B, H, W, c), window, stride, wrap, weights)
+    else:
+      ops.window_fold(self._eps_win, self._eps.view(2, B, H, W, c), window, stride)
     self._update(guidance_scale, False, noise_table, dec_index, None, rng=rng)
 
+  def _finish_wrapped(self, latents, pad):
+    """_finish for a wrapped canvas: the decoder's zero-padded convolutions see across the wrap
+    through `pad` = (py, px) cells of circular padding, whose pixels are cropped from the images."""
+    py, px = pad
+    B, H, W, c = (int(v) for v in latents.shape)
+    try:
+      images = self._finish(ops.wrap_pad(latents, pad) if py or px else latents)
+    except LdmHipError as e:
+      raise ValueError(f"the decoder cannot decode a canvas of shape {[B, H + 2 * py, W + 2 * px, c]}: {e}") from e
+    if not (py or px):
+      return images
+    f = self._pixel_factor()
+    return images[:, py * f:(py + H) * f, px * f:(px + W) * f].contiguous()
+
   def ddim_p_sample_loop_panorama(self, cond_model_inputs, shape, window, stride=None, guidance_scale=5., x_T=None,
-                                  noises=None, seed=0, first_sample_index=0, record=None, guidance_interval=None):
+                                  noises=None, seed=0, first_sample_index=0, record=None, guidance_interval=None,
+                                  wrap=(False, False), window_weights="uniform", wrap_decode_margin=0):
     """MultiDiffusion (Bar-Tal et al. 2023) on the loop of ddim_p_sample_loop.  `shape` is the
     canvas [B,H,W,c]; `window` = (h, w) the size the U-Net runs at; `stride` = (sy, sx), default half the window
     (at least 1); one int means both axes.  Windows lie at window_origins() along each axis, the last one clamped to the edge.  Every step
     evaluates the U-Net on the 2 * B * nW window rows and steps the canvas once with the mean eps of the windows
     covering each cell.  x_T, noises ([N,B,H,W,c]), seed and record are the canvas's, as in ddim_p_sample_loop; every
     sampler=, step table and noise source runs.  A window equal to the canvas is ddim_p_sample_loop bit for bit.
-    `guidance_scale` is one float: schedules (a sequence, `guidance_interval`) are not supported here."""
+    `guidance_scale` is one float: schedules (a sequence, `guidance_interval`) are not supported here.
+    Seamless panoramas: `wrap` = (wrap_y, wrap_x) lays the windows of a wrapped axis at
+    wrap_origins(), crossing the edge and coming back on the other side.  `window_weights`: "uniform" (the plain
+    mean), "tent", "gaussian" (window_profile) or a pair of positive arrays (wy [h], wx [w]): the fold is the mean
+    weighted by wy[jy] * wx[jx] at each window element.  `wrap_decode_margin`: latent cells of circular padding the
+    decoder sees on each side of a wrapped axis (cropped from the images; 0 = the plain decode)."""
     if np.ndim(guidance_scale) > 0 or guidance_interval is not None:
       raise ValueError("the panorama loop takes one float guidance_scale: a sequence guidance_scale or a "
                        "guidance_interval is not supported")
     B, H, W, c = (int(s) for s in shape)
     (h, w), (sy, sx) = window_and_stride(window, stride)
-    n_win = len(window_origins(H, h, sy)) * len(window_origins(W, w, sx))        # (ValueError: no such grid)
+    wrap = wrap_pair(wrap)
+    # (ValueError: no such grid)
+    n_win = (len((wrap_origins if wrap[0] else window_origins)(H, h, sy)) *
+             len((wrap_origins if wrap[1] else window_origins)(W, w, sx)))
+    profile, tables = window_weight_tables(window_weights, (h, w))
+    margin = int(wrap_decode_margin)
+    if margin != wrap_decode_margin or margin < 0:
+      raise ValueError(f"wrap_decode_margin must be an int of at least 0, got {wrap_decode_margin!r}")
+    pad = (margin if wrap[0] else 0, margin if wrap[1] else 0)
+    if pad[0] > H or pad[1] > W:
+      raise ValueError(f"wrap_decode_margin {margin} exceeds the canvas extent along a wrapped axis ({H}x{W})")
     context = self._cond_stage_model(cond_model_inputs)
     n = len(self._ddim_steps)
     xt = self._x_T(x_T, seed, first_sample_index, B, H, W, c)
     self._alloc_state(B, H, W, c)
     self._alloc_windows(B, n_win, h, w, c)
+    weights = None
+    if tables is not None:                           # (owned: the captured fold reads them at fixed addresses)
+      weights = (self._owned("_win_wy", tables[0], (h,)), self._owned("_win_wx", tables[1], (w,)))
     # row (half, b, k) of the window batch attends to context[half * B + b]
     context = torch.as_tensor(context).to(self.device)
     if context.shape[0] != 2 * B:
@@ -1374,13 +1484,10 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       self._set_loop_start(n - 1)
 
     gkey = ("panorama", (B, H, W, c), (h, w), (sy, sx), float(guidance_scale), noise_table is not None,
-            self._ctx_shape, False, self._noise_source, rng, self._step_spacing, self._sampler)
+            self._ctx_shape, False, self._noise_source, rng, self._step_spacing, self._sampler, wrap, profile)
     self._sample_loop(n, reset, lambda dec: self._step_panorama(guidance_scale, noise_table, dec, (h, w), (sy, sx),
-                                                                rng=rng), gkey, record)
-    try:
-      return self._finish(self._xt)
-    except LdmHipError as e:
-      raise ValueError(f"the decoder cannot decode a canvas of shape {[B, H, W, c]}: {e}") from e
+                                                                rng=rng, wrap=wrap, weights=weights), gkey, record)
+    return self._finish_wrapped(self._xt, pad)
 
   def ddim_p_sample_loop_progressive(self, cond_model_inputs, shape, guidance_scale=5.,
                                      record_freq=5, x_T=None, noises=None, seed=0,

@@ -21,7 +21,7 @@ __all__ = [
     "bmm_nt", "conv3x3_small", "groupnorm", "layernorm", "softmax_rows", "attention",
     "time_embedding", "gemv", "cfg_ddim_update", "cfg_ddim_update_masked", "cfg_plms_update", "q_sample",
     "philox_u32", "normal_fill", "q_sample_rng", "cfg_ddim_update_rng", "cfg_plms_update_rng", "cfg_ms_update",
-    "cfg_ms_update_rng", "cfg_sched_update", "cfg_ddim_invert_update", "window_gather", "window_fold", "resize_nhwc", "resample_nhwc", "post_quant", "vq_nearest", "embedding",
+    "cfg_ms_update_rng", "cfg_sched_update", "cfg_ddim_invert_update", "window_gather", "window_fold", "window_gather_ex", "window_fold_ex", "wrap_pad", "resize_nhwc", "resample_nhwc", "post_quant", "vq_nearest", "embedding",
     "minmax_u8", "cast",
 ]
 
@@ -1070,6 +1070,60 @@ def window_fold(eps_win, eps_canvas, window, stride):
   check(lib.ldm_window_fold(_ptr(_f32(eps_win, "eps_win")), _ptr(_f32(eps_canvas, "eps_canvas")), halves, *dims,
                             _stream()), "ldm_window_fold")
   return eps_canvas
+
+
+def _window_args_ex(canvas, win, lead, window, stride, wrap, what):
+  """_window_args for a grid with `wrap` = (wrap_y, wrap_x): a wrapped axis has ceil(L / s) windows."""
+  (h, w), (sy, sx), (wy, wx) = (int(v) for v in window), (int(v) for v in stride), (int(bool(v)) for v in wrap)
+  B, H, W, c = (int(v) for v in canvas.shape[-4:])
+  assert canvas.is_contiguous() and win.is_contiguous(), what
+  if 1 <= h <= H and 1 <= w <= W and 1 <= sy <= h and 1 <= sx <= w:
+    n = lambda L, l, s, wr: -(-L // s) if wr else -((l - L) // s) + 1
+    n_win = n(H, h, sy, wy) * n(W, w, sx, wx)
+    assert win.numel() == lead * B * n_win * h * w * c, (what, tuple(win.shape), (lead, B, n_win, h, w, c))
+  return B, H, W, c, h, w, sy, sx, wy, wx
+
+
+def window_gather_ex(canvas, x_win, window, stride, wrap):
+  """window_gather with `wrap` = (wrap_y, wrap_x): along a wrapped axis the windows lie at
+  i * stride without a clamp and cover the cells modulo the extent."""
+  assert canvas.dim() == 4, tuple(canvas.shape)
+  dims = _window_args_ex(canvas, x_win, 2, window, stride, wrap, "window_gather_ex")
+  check(lib.ldm_window_gather_ex(_ptr(_f32(canvas, "canvas")), _ptr(x_win), code(x_win.dtype), *dims, _stream()),
+        "ldm_window_gather_ex")
+  return x_win
+
+
+def window_fold_ex(eps_win, eps_canvas, window, stride, wrap, weights=None):
+  """window_fold on the grid of window_gather_ex with `weights` = (wy [h], wx [w]) float32 device tables of positive
+  window-profile weights: every canvas element the float32 sum(wy wx v) / sum(wy wx) over the covering windows
+  (ascending window index, every operation rounded once).  None: uniform, window_fold's arithmetic."""
+  assert eps_canvas.dim() == 5, tuple(eps_canvas.shape)
+  halves = int(eps_canvas.shape[0])
+  dims = _window_args_ex(eps_canvas, eps_win, halves, window, stride, wrap, "window_fold_ex")
+  wy, wx = (None, None) if weights is None else weights
+  for t, n, what in ((wy, dims[4], "wy"), (wx, dims[5], "wx")):
+    assert t is None or (t.is_contiguous() and t.numel() == n), (what, tuple(t.shape), n)
+  check(lib.ldm_window_fold_ex(_ptr(_f32(eps_win, "eps_win")), _ptr(_f32(eps_canvas, "eps_canvas")), halves, *dims,
+                               _ptr(_f32(wy, "wy")), _ptr(_f32(wx, "wx")), _stream()), "ldm_window_fold_ex")
+  return eps_canvas
+
+
+def wrap_pad(x, pad, out=None):
+  """Circular padding (include/ldm_hip.h): x [B,H,W,c] float32 -> [B,H+2py,W+2px,c] float32,
+  `pad` = (py, px), out[b,y,x] = x[b,(y-py) mod H,(x-px) mod W].  `out`: where the result goes (contiguous;
+  allocated when omitted)."""
+  assert x.dim() == 4 and x.is_contiguous(), (tuple(x.shape), x.stride())
+  B, H, W, c = (int(v) for v in x.shape)
+  py, px = (int(v) for v in pad)
+  shape = (B, H + 2 * max(py, 0), W + 2 * max(px, 0), c)
+  if out is None:
+    out = torch.empty(shape, dtype=torch.float32, device=x.device)
+  elif 0 <= py <= H and 0 <= px <= W:
+    assert out.is_contiguous() and tuple(out.shape) == shape, (tuple(out.shape), shape)
+  check(lib.ldm_wrap_pad_nhwc(_ptr(_f32(x, "x")), _ptr(_f32(out, "out")), B, H, W, c, py, px, _stream()),
+        "ldm_wrap_pad_nhwc")
+  return out
 
 
 def resize_nhwc(x, size, mode, out=None):

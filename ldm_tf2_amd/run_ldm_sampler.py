@@ -43,6 +43,11 @@ Panorama: optional `ldm_sampling` keys `window: [h, w]` and `window_stride: [sy,
 `window`-sized crops of the canvas and averages their predictions where they overlap (MultiDiffusion; DESIGN.md
 section 12).  Every solver, step table and noise source runs; `init_image`, `mask`, `sample_save_progress`,
 `guidance_interval` and a list `guidance_scale` cannot be combined with it.  Without `window` nothing changes.
+Seamless panoramas, each key needing `window`: `window_wrap: [wrap_y, wrap_x]` (bools) lets the
+windows of an axis cross the edge and come back on the other side (a 360-degree panorama, a tileable texture);
+`window_weights: uniform | tent | gaussian` weights each window by a profile that falls off towards its border instead
+of the plain mean; `wrap_decode_margin: m` decodes the canvas with m latent cells of circular padding on each side of
+a wrapped axis and crops them from the images, so the decoder sees across the wrap column.
 
 Prompt editing: optional `ldm_sampling` key `source_prompt` (a string; needs `init_image`).  The init image is encoded,
 inverted `int(strength * N)` DDIM steps under `source_prompt` (DDIM inversion, guidance scale `invert_guidance_scale`,
@@ -78,7 +83,8 @@ import yaml
 from . import ops
 from .autoencoder import AutoencoderKL, AutoencoderVQ
 from ._lib import RESAMPLE_FILTERS
-from .model_runners import FITS, RESIZE_MODES, LatentDiffusionModelSampler, latent_mask, window_and_stride
+from .model_runners import (FITS, RESIZE_MODES, WINDOW_WEIGHTS, LatentDiffusionModelSampler, latent_mask,
+                            window_and_stride)
 from .tokenizer import get_token_ids
 from .transformer import TransformerModel
 from .unet import UNet
@@ -199,7 +205,34 @@ def panorama_kwargs(config, seed):
     if v is not None and (not isinstance(v, (list, tuple)) or len(v) != 2):
       raise ValueError(f"ldm_sampling.{key} must be a pair of ints, got {v!r}")
   window, stride = window_and_stride(samp["window"], samp.get("window_stride"))
-  return dict(window=window, stride=stride, seed=seed)
+  return dict(window=window, stride=stride, seed=seed, **panorama_wrap_kwargs(config))
+
+
+PANORAMA_WRAP_KEYS = ("window_wrap", "window_weights", "wrap_decode_margin")
+
+
+def panorama_wrap_kwargs(config):
+  """`ldm_sampling.window_wrap: [bool, bool]`, `window_weights: uniform | tent | gaussian` and `wrap_decode_margin:
+  int` as the panorama loop's keywords (the reference's YAML has no such keys); nothing for a
+  key that is absent."""
+  samp = config["ldm_sampling"]
+  kwargs = {}
+  v = samp.get("window_wrap")
+  if v is not None:
+    if not isinstance(v, (list, tuple)) or len(v) != 2 or any(not isinstance(x, bool) for x in v):
+      raise ValueError(f"ldm_sampling.window_wrap must be a pair of bools [wrap_y, wrap_x], got {v!r}")
+    kwargs["wrap"] = (v[0], v[1])
+  v = samp.get("window_weights")
+  if v is not None:
+    if v not in WINDOW_WEIGHTS:
+      raise ValueError(f"ldm_sampling.window_weights must be one of {WINDOW_WEIGHTS}, got {v!r}")
+    kwargs["window_weights"] = v
+  v = samp.get("wrap_decode_margin")
+  if v is not None:
+    if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+      raise ValueError(f"ldm_sampling.wrap_decode_margin must be an int of at least 0, got {v!r}")
+    kwargs["wrap_decode_margin"] = v
+  return kwargs
 
 
 def hires_call(config, token_ids, seed):
@@ -262,6 +295,9 @@ def sampling_call(config, token_ids, seed, source_ids=None):
   samp = config["ldm_sampling"]
   base = (token_ids, samp["latent_shape"], samp["guidance_scale"])
   init_fit_kwargs(config)                        # (ValueError: an unknown init_fit or init_filter, whatever the loop)
+  for key in PANORAMA_WRAP_KEYS:
+    if samp.get(key) is not None and samp.get("window") is None:
+      raise ValueError(f"ldm_sampling.{key} needs ldm_sampling.window")
   if samp.get("hires_shape") is not None:
     return hires_call(config, token_ids, seed)
   if samp.get("hires_pixel_filter") is not None:
