@@ -238,6 +238,10 @@ int ldm_groupnorm_apply(const void* x, int64_t ldx, const float* partial, const 
  * and written once, and the variance is the two-pass (centred) form.  _supported is a pure
  * host query; ldm_groupnorm_fused fails (LDM_ERR_ARG) on an unsupported shape. */
 int ldm_groupnorm_fused_supported(int B, int HW, int C, int groups, int dtype);
+/* the launch form ldm_groupnorm_fused runs for this shape (host query, the plan of the launch itself):
+ * form[4] = {GB, S, NT, MAXCH} as ldm_groupnorm_splitk_form; LDM_OK, or LDM_ERR_ARG when the shape is not
+ * supported (form untouched) */
+int ldm_groupnorm_fused_form(int B, int HW, int C, int groups, int dtype, int* form);
 int ldm_groupnorm_fused(const void* x, int64_t ldx, const float* gamma, const float* beta, void* out,
                         int64_t ldo, int B, int HW, int C, int groups, float eps, int silu, int dtype,
                         void* stream);

@@ -52,10 +52,8 @@ inline bool gn_fused_plan(int B, int HW, int C, int G, int esize, GnFusedPlan* p
     if (need <= 8) { *pl = {GB, S, NT, 8}; return true; }
     if (need <= 16) { *pl = {GB, S, NT, 16}; return true; }
   }
-  for (int NT : {256, 512}) {
-    const int need = (HW + NT / S - 1) / (NT / S);
-    if (need <= 24) { *pl = {GB, S, NT, 24}; return true; }
-  }
+  // (24 chunks per thread at 256 or 512 threads cannot occur: floor(1024 / S) >= 4 floor(256 / S) and
+  // >= 2 floor(512 / S), so a slab that needs more than 16 chunks at 1024 threads needs more than 64 / 32 there)
   return false;
 }
 
@@ -322,8 +320,8 @@ void gn_fused_launch(const GnFusedPlan& pl, dim3 grid, hipStream_t s, const void
   hipLaunchKernelGGL((gn_fused_kernel<T, NT_, MC_, SK>), grid, dim3(NT_), 0, s, (const T*)x, ldx, gamma,   \
                      beta, (T*)out, ldo, B, HW, C, G, pl.GB, pl.S, eps, silu, sk)
   if (pl.NT == 64) { if (pl.maxch == 8) GNF(64, 8); else if (pl.maxch == 16) GNF(64, 16); else GNF(64, 24); }
-  else if (pl.NT == 256) { if (pl.maxch == 8) GNF(256, 8); else if (pl.maxch == 16) GNF(256, 16); else GNF(256, 24); }
-  else if (pl.NT == 512) { if (pl.maxch == 8) GNF(512, 8); else if (pl.maxch == 16) GNF(512, 16); else GNF(512, 24); }
+  else if (pl.NT == 256) { if (pl.maxch == 8) GNF(256, 8); else GNF(256, 16); }
+  else if (pl.NT == 512) { if (pl.maxch == 8) GNF(512, 8); else GNF(512, 16); }
   else { if (pl.maxch == 8) GNF(1024, 8); else GNF(1024, 16); }
 #undef GNF
 }

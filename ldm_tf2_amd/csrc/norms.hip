@@ -294,6 +294,14 @@ extern "C" int ldm_groupnorm_fused_supported(int B, int HW, int C, int groups, i
   return gn_fused_plan(B, HW, C, groups, dtype == LDM_BF16 ? 2 : 4, &pl) ? 1 : 0;
 }
 
+extern "C" int ldm_groupnorm_fused_form(int B, int HW, int C, int groups, int dtype, int* form) {
+  GnFusedPlan pl;
+  if (!form || !(dtype == LDM_F32 || dtype == LDM_BF16) || B <= 0 || HW <= 0 || C <= 0) return LDM_ERR_ARG;
+  if (!gn_fused_plan(B, HW, C, groups, dtype == LDM_BF16 ? 2 : 4, &pl)) return LDM_ERR_ARG;
+  form[0] = pl.GB; form[1] = pl.S; form[2] = pl.NT; form[3] = pl.maxch;
+  return LDM_OK;
+}
+
 extern "C" int ldm_groupnorm_fused(const void* x, int64_t ldx, const float* gamma, const float* beta,
                                    void* out, int64_t ldo, int B, int HW, int C, int groups, float eps,
                                    int silu, int dtype, void* stream) {
