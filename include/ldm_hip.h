@@ -659,6 +659,31 @@ int ldm_resample_nhwc(const float* x, float* tmp, float* out, int B, int H, int 
                       const int32_t* xstart, const float* xw, int xtaps, const int32_t* ystart, const float* yw,
                       int ytaps, void* stream);
 
+/*
+ * Latent previews: small RGB pictures of one or two latent tensors, written into a strip of
+ * frames whose slot a device-resident index selects, so that the launch can sit inside a captured sampling step.
+ *   lat_a, lat_b [B][h][w][c] float32 (lat_b may be NULL); proj [c + 1][3] float32: c weight rows, then the bias row;
+ *   frames_a, frames_b [R][B][s h][s w][3] uint8, s = scale (frames_b NULL exactly when lat_b is).
+ * Slot rule: idx = (index ? *index : 0) + index_bias.  idx < 0, idx % freq != 0 or idx / freq >= R: the launch writes
+ * nothing at all.  Otherwise it writes slot r = idx / freq, and that slot alone, of every source present.
+ * Per output byte k of pixel (y, x): for j = 0 .. c-1 in turn a_j = the latent channel j enlarged s times at (y, x) --
+ * LDM_PREVIEW_NEAREST: lat[y / s][x / s][j]; LDM_PREVIEW_BILINEAR: the taps, clamps and fractions of LDM_RESIZE_BILINEAR
+ * at Lo = s L, a_j = fma(wy wx, lat, a_j) from 0, rows outermost -- and v_k = fma(a_j, proj[j][k], v_k) from v_k =
+ * proj[c][k]; t = fma(127.5, v_k, 127.5); the byte is floor(min(max(t, 0), 255) + 0.5), a NaN giving 0 through the max.
+ * All float32.  scale 1 is the nearest rule in both modes (the weights are 1 and 0).
+ *
+ * A thread owns four consecutive pixels of the slot's flat pixel run (12 bytes): three dword stores where the slot's
+ * first byte is 4-byte aligned, byte stores otherwise and for a last partial group, the same bytes either way.  No
+ * atomics, no tables: the result is deterministic.  c = 4 and c = 3 keep proj in registers; any other c reads it in the
+ * channel loop.  LDM_ERR_ARG, nothing launched: a null lat_a, proj or frames_a; one of lat_b and frames_b without the
+ * other; an unknown mode; c or scale outside 1..16; freq or R below 1; B, h or w below 1.
+ */
+#define LDM_PREVIEW_NEAREST 0
+#define LDM_PREVIEW_BILINEAR 1
+int ldm_latent_preview(const float* lat_a, const float* lat_b, const float* proj, uint8_t* frames_a, uint8_t* frames_b,
+                       const int32_t* index, int index_bias, int freq, int R, int B, int h, int w, int c, int scale,
+                       int mode, void* stream);
+
 /* decode_first_stage prologue (model_runners.py:426 + autoencoder.py:362,434):
  * out = Dense_{C->C}(latents / scale_factor), C <= 8; float32 in, out_dtype out. */
 int ldm_post_quant(const float* latents, float scale_factor, const float* kernel_io,

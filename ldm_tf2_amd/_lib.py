@@ -18,6 +18,7 @@ F32, BF16 = 0, 1
 ACT_NONE, ACT_GELU, ACT_GEGLU, ACT_SILU = 0, 1, 2, 3
 OK, ERR_ARG, ERR_LAUNCH, ERR_WORKSPACE = 0, -1, -2, -3     # include/ldm_hip.h status codes
 RESIZE_MODES = {"nearest": 0, "bilinear": 1, "bicubic": 2}  # LDM_RESIZE_*
+PREVIEW_MODES = {"nearest": 0, "bilinear": 1}               # LDM_PREVIEW_*
 RESAMPLE_FILTERS = ("triangle", "cubic", "lanczos3")        # ldm_resample_nhwc's tables (resample.py)
 
 c_i64, c_i32, c_f32, c_vp, c_sz = C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_size_t
@@ -119,6 +120,8 @@ SIGNATURES = {
     "ldm_resize_nhwc": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "ldm_resample_nhwc": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp,
                                   c_vp, c_i32, c_vp]),
+    "ldm_latent_preview": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                   c_i32, c_i32, c_vp]),
     "ldm_post_quant": (c_i32, [c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp]),
     "ldm_groupnorm_fused_supported": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32]),
     "ldm_groupnorm_fused_form": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i32)]),

@@ -59,6 +59,12 @@ without an encoder.  The sampler keeps the device state and the captured graphs 
 image_size= / fit= / resample= on the image-driven loops, and pixel_filter= on the two-pass loop
 bring init images, pixel masks and pass 1's decoded image to the size the models need with the antialiased resample
 (ldm_resample_nhwc, tables from resample.py) on the device, next to the encoder.
+
+preview_freq= / on_preview= on ddim_p_sample_loop and ddim_p_sample_loop_img2img record small
+RGB pictures of x_t and of the predicted x_0 every q DDIM indices: the step's update also writes pred_x0 and one
+ldm_latent_preview launch inside the captured step maps both through the matrix of set_preview / fit_preview, enlarges
+and quantises them into the slot the device-resident index selects.  Those steps are captured in graph slots of their
+own; without the keyword every key, launch and graph is the one it was.
 """
 from __future__ import annotations
 
@@ -103,6 +109,7 @@ def normal_latents(seed, first_index, count, shape_hwc, stream=None):
 
 ENCODE_STREAM = 1 << 30          # posterior noise E of get_latents
 Q_STREAM = (1 << 30) + 1         # + i: forward-diffusion noise Q[i] of DDIM index i
+PREVIEW_FIT_STREAM = 1 << 31     # the stand-in latents of fit_preview (above Q_STREAM + i for every i < 2^30)
 # noise_source="device" only (the host draws key x_T and the eta noise by the seed word, see normal_latents): the
 # stream word is the third counter word of the device generator; the four ranges are disjoint for i < 2^29.
 XT_STREAM = 0                    # x_T
@@ -333,6 +340,40 @@ def guidance_table(steps, guidance_scale, guidance_interval=None):
   if not np.all(np.isfinite(g)):
     raise ValueError("guidance_scale must be finite (as float32)")
   return g
+
+
+PREVIEW_MODES = ("nearest", "bilinear")
+
+
+def fit_latent_preview(latents, images):
+  """The latent-to-RGB matrix of the previews, float32 [c+1,3]: c weight rows, then the bias
+  row.  `latents` [n,h,w,c] and `images` [n,f*h,f*w,3] (the decoder's, in [-1, 1]): the f x f block mean of the
+  images is regressed on [latents, 1] by least squares, in float64.  ValueError: image extents that are not one
+  integer multiple f of the latents', or a design matrix of rank below c + 1 (fewer than c + 1 cells, or channels
+  that are affinely dependent)."""
+  lat = np.asarray(latents.detach().float().cpu() if isinstance(latents, torch.Tensor) else latents, dtype=np.float64)
+  img = np.asarray(images.detach().float().cpu() if isinstance(images, torch.Tensor) else images, dtype=np.float64)
+  if lat.ndim != 4 or img.ndim != 4 or img.shape[0] != lat.shape[0] or img.shape[3] != 3:
+    raise ValueError(f"fit_latent_preview: latents {lat.shape} must be [n,h,w,c] and images {img.shape} [n,f*h,f*w,3]")
+  n, h, w, c = lat.shape
+  if min(n, h, w, c) < 1:
+    raise ValueError(f"fit_latent_preview: empty latents {lat.shape}")
+  f = img.shape[1] // h
+  if f < 1 or img.shape[1] != f * h or img.shape[2] != f * w:
+    raise ValueError(f"fit_latent_preview: image extents {img.shape[1:3]} are not one integer multiple of the "
+                     f"latent extents {(h, w)}")
+  target = img.reshape(n, h, f, w, f, 3).mean(axis=(2, 4)).reshape(-1, 3)
+  design = np.concatenate([lat.reshape(-1, c), np.ones((n * h * w, 1))], axis=1)
+  sol, _, rank, _ = np.linalg.lstsq(design, target, rcond=None)
+  if rank < c + 1:
+    raise ValueError(f"fit_latent_preview: the design matrix [latents, 1] of shape {design.shape} has rank {rank}, "
+                     f"below {c + 1}: the fit is not determined")
+  return sol.astype(np.float32)
+
+
+def preview_slots(num_ddim_steps, freq):
+  """R = (N - 1) // q + 1: the slots of a preview strip; slot r holds the step at DDIM index r * q."""
+  return (int(num_ddim_steps) - 1) // int(freq) + 1
 
 
 class LatentDiffusionModel(object):
@@ -590,6 +631,15 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     self._inv_graph_key = None                   # with the sampling graphs above
     self._inv_tbl = None
     self._inv_temb = None
+    self._pv_graph = None                        # the steps captured with previews have slots
+    self._pv_graph_key = None                    # of their own: a loop without previews finds its graph as it left it
+    self._pv_sched_graphs = {}
+    self._pv_sched_key = None
+    self._pv_proj = None                         # set_preview: the matrix on the device, the scale and the mode
+    self._pv_host = None
+    self._pv_scale = None
+    self._pv_mode = "bilinear"
+    self._pv_last = None
     self.last_step_ms = None
 
   # ---- the steps' temb projections, once per sampler ---------------------------------
@@ -615,8 +665,9 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
   # wait in _states, so a sampler that alternates between two shapes allocates and captures each
   # once.  What the graphs of every shape read alike (_rng, _gtab, the tables, the device counter) is not listed.
   _SHAPE_BUFFERS = ("_xt", "_x2", "_eps", "_ring", "_start", "_noise_buf", "_q_buf", "_z0_buf", "_mask_buf", "_t_buf",
-                    "_x_win", "_eps_win", "_win_key", "_win_wy", "_win_wx")
-  _SHAPE_GRAPHS = ("_graph", "_graph_key", "_sched_graphs", "_sched_key", "_inv_graph", "_inv_graph_key")
+                    "_x_win", "_eps_win", "_win_key", "_win_wy", "_win_wx", "_pv_x0", "_pv_a", "_pv_b")
+  _SHAPE_GRAPHS = ("_graph", "_graph_key", "_sched_graphs", "_sched_key", "_inv_graph", "_inv_graph_key",
+                   "_pv_graph", "_pv_graph_key", "_pv_sched_graphs", "_pv_sched_key")
 
   def _alloc_state(self, B, h, w, c):
     key = (B, h, w, c)
@@ -633,7 +684,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
           setattr(self, n, v)
         self._state_key = key
         return
-      self._graph_key = self._sched_key = self._inv_graph_key = None
+      self._graph_key = self._sched_key = self._inv_graph_key = self._pv_graph_key = self._pv_sched_key = None
       dev, f32 = self.device, torch.float32
       self._xt = torch.empty(B, h, w, c, dtype=f32, device=dev)
       self._x2 = torch.empty(2 * B, h, w, c, dtype=f32, device=dev)
@@ -659,6 +710,105 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     self._graph = None
     self._sched_graphs = {}
     self._inv_graph = None
+    self._pv_graph = None
+    self._pv_sched_graphs = {}
+
+  # ---- latent previews --------------------------------------------------
+  def set_preview(self, proj, scale=None, mode="bilinear"):
+    """The previews' latent-to-RGB matrix `proj` [c+1,3] (c weight rows, then the bias; fit_latent_preview's result),
+    the integer upscale `scale` (None: the autoencoder's pixels per latent cell, so a preview has the image's size) and
+    the upscale `mode`, "nearest" or "bilinear".  Changing any of the three drops the steps captured with previews, of
+    every latent shape, and no other graph; the same three again change nothing."""
+    if mode not in PREVIEW_MODES:
+      raise ValueError(f"preview mode must be one of {PREVIEW_MODES}, got {mode!r}")
+    scale = self._pixel_factor() if scale is None else scale
+    if isinstance(scale, bool) or int(scale) != scale or not 1 <= int(scale) <= 16:
+      raise ValueError(f"preview scale must be an int in [1, 16], got {scale!r}")
+    proj = np.asarray(proj.detach().cpu() if isinstance(proj, torch.Tensor) else proj, dtype=np.float32)
+    if proj.ndim != 2 or proj.shape[1] != 3 or not 2 <= proj.shape[0] <= 17:
+      raise ValueError(f"preview matrix must be [c+1,3] with c in [1, 16], got {proj.shape}")
+    if not np.isfinite(proj).all():
+      raise ValueError("preview matrix must be finite")
+    same = (self._pv_proj is not None and (int(scale), mode) == (self._pv_scale, self._pv_mode) and
+            np.array_equal(self._pv_host, proj))
+    if same:
+      return
+    # (a new tensor: the graphs that read the old one go with it)
+    self._pv_host = proj.copy()
+    self._pv_proj = torch.from_numpy(self._pv_host).to(self.device).contiguous()
+    self._pv_scale, self._pv_mode = int(scale), mode
+    self._pv_graph, self._pv_sched_graphs = None, {}
+    for saved in self._states.values():
+      saved.update({"_pv_graph": None, "_pv_sched_graphs": {}})
+
+  def fit_preview(self, latents=None, n=8, seed=0, shape=None):
+    """Fits the previews' matrix on this sampler's own decoder and stores it (set_preview, keeping the scale and mode
+    already set): `latents` [n,h,w,c], scaled as the loops' latents are, are decoded with decode_first_stage and
+    handed to fit_latent_preview.  Without `latents`, `n` draws of N(0,1) (normal_latents under a key derived from
+    `seed`: its stream PREVIEW_FIT_STREAM) at `shape` = (h, w, c) stand in for them -- default: the latent shape of
+    the last loop, else the size the autoencoder is bound to, else 32 x 32, with the autoencoder's latent channels
+    (the U-Net itself carries no size).  That default is rough: white noise
+    is not what the loops' latents look like, and a matrix fitted on a run's final latents (tools/fit_preview.py)
+    gives truer colours.  Returns the float32 [c+1,3] matrix."""
+    if latents is None:
+      if shape is None:
+        if self._state_key is not None:
+          shape = self._state_key[1:]
+        else:
+          side = getattr(self._autoencoder, "_latent_size", None) or 32
+          shape = (side, side, getattr(self._autoencoder, "_latent_channels", 4))
+      latents = normal_latents(seed, 0, int(n), tuple(int(v) for v in shape), stream=PREVIEW_FIT_STREAM)
+    lat = torch.as_tensor(np.asarray(latents) if not isinstance(latents, torch.Tensor) else latents,
+                          dtype=torch.float32).to(self.device).contiguous()
+    images = self.decode_first_stage(lat)
+    proj = fit_latent_preview(lat, images)
+    self.set_preview(proj, scale=self._pv_scale, mode=self._pv_mode)
+    return proj
+
+  def _preview_on(self, preview_freq, on_preview, N):
+    """The checked `preview_freq` of a loop call: None (no previews; `on_preview` needs them) or q >= 1, with the
+    current shape's pred_x0 buffer and the two strips [R,B,s*h,s*w,3] allocated (after _alloc_state)."""
+    if preview_freq is None:
+      if on_preview is not None:
+        raise ValueError("on_preview needs preview_freq")
+      return None
+    q = int(preview_freq)
+    if isinstance(preview_freq, bool) or q != preview_freq or q < 1:
+      raise ValueError(f"preview_freq must be an int of at least 1, got {preview_freq!r}")
+    if self._pv_proj is None:
+      raise ValueError("preview_freq needs a preview matrix: call set_preview or fit_preview first")
+    B, h, w, c = self._xt.shape
+    if self._pv_proj.shape[0] != c + 1:
+      raise ValueError(f"the preview matrix is {tuple(self._pv_proj.shape)}, latents with {c} channels need {(c + 1, 3)}")
+    s = self._pv_scale
+    shape = (preview_slots(N, q), B, s * h, s * w, 3)
+    if getattr(self, "_pv_a", None) is None or tuple(self._pv_a.shape) != shape:
+      self._pv_x0 = torch.empty(B, h, w, c, dtype=torch.float32, device=self.device)
+      self._pv_a = torch.zeros(shape, dtype=torch.uint8, device=self.device)
+      self._pv_b = torch.zeros(shape, dtype=torch.uint8, device=self.device)
+      self._pv_graph, self._pv_sched_graphs = None, {}           # (the captured launches wrote the old strips)
+    return q
+
+  def _preview_step(self, q, dec_index):
+    """The step's one extra launch: _xt and the step's pred_x0 into the slot of the step's DDIM index.  After the
+    update the counter holds that index when the U-Net's first launch pre-decremented it, and one less when the
+    update itself moved it (temb_table=False); the uncounted warm-up step moves nothing."""
+    ops.latent_preview(self._xt, self._pv_proj, self._pv_a, q, index=self._index_dev,
+                       index_bias=1 if dec_index and not self._pre_dec else 0, lat_b=self._pv_x0,
+                       frames_b=self._pv_b, scale=self._pv_scale, mode=self._pv_mode)
+
+  def last_previews(self):
+    """The strips of the last loop run with preview_freq = q: dict(sample=, pred_x0=) uint8 NumPy [B,R,H,W,3] (x_t
+    after, and the predicted x_0 of, the step at DDIM index r * q), indices= int [R] (r * q) and written= bool [R]
+    (False: a slot above the loop's first index, left at 0).  Synchronises."""
+    if self._pv_last is None:
+      raise ValueError("no loop has run with preview_freq")
+    q, k, a, b = self._pv_last
+    R = a.shape[0]
+    indices = np.arange(R) * q
+    return dict(sample=np.ascontiguousarray(a.cpu().numpy().swapaxes(0, 1)),
+                pred_x0=np.ascontiguousarray(b.cpu().numpy().swapaxes(0, 1)), indices=indices,
+                written=indices <= k - 1)
 
   def _set_loop_start(self, start_index):
     """PLMS / DEIS: the loop's first step is the one at DDIM index `start_index` (it has no history)."""
@@ -779,18 +929,22 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
                          dec_index=dec_index and not self._pre_dec, pred_x0_out=pred_x0_out, **hist,
                          **self._blend_kwargs(masked, rng))
 
-  def _sample_loop_sched(self, forms, reset, step, gkey, record):
+  def _sample_loop_sched(self, forms, reset, step, gkey, record, slot="_sched", after_step=None):
     """_sample_loop for a guidance schedule: forms[s] = whether the s-th step of the loop is guided (host-known when
     the loop starts; the index stays on the device); `step(guided, dec_index)` enqueues one step.  With graphs, one
     step per form in use is captured once per `gkey` and the host replays whichever form each step takes.  Events
-    around every contiguous run of one form give the per-form times (last_form_ms_per_step)."""
+    around every contiguous run of one form give the per-form times (last_form_ms_per_step).  `slot`: the attributes
+    that keep the graphs and their key (`slot`_graphs, `slot`_key), as in _sample_loop; `after_step(s)` runs on the
+    host after the s-th step is enqueued."""
     num_steps = len(forms)
     reset()
     use_graph = self._use_graph and record is None
     if use_graph:
-      if self._sched_key != gkey:
-        self._sched_graphs, self._sched_key = {}, gkey
-      for guided in sorted(set(forms) - set(self._sched_graphs), reverse=True):
+      if getattr(self, slot + "_key") != gkey:
+        setattr(self, slot + "_graphs", {})
+        setattr(self, slot + "_key", gkey)
+      graphs = getattr(self, slot + "_graphs")
+      for guided in sorted(set(forms) - set(graphs), reverse=True):
         self._index_dev.fill_(num_steps - 1)         # (the warm-up step does not move the counter)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -802,17 +956,19 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, capture_error_mode="thread_local"):
           step(guided, True)
-        self._sched_graphs[guided] = g
+        graphs[guided] = g
         reset()
     marks = [(torch.cuda.Event(enable_timing=True), None)]
     marks[0][0].record()
     for i, guided in enumerate(forms):
       if use_graph:
-        self._sched_graphs[guided].replay()
+        graphs[guided].replay()
       else:
         step(guided, True)
         if record is not None:
           record.append(self._xt.clone())
+      if after_step is not None:
+        after_step(i)
       if i + 1 == num_steps or forms[i + 1] != guided:
         ev = torch.cuda.Event(enable_timing=True)
         ev.record()
@@ -905,12 +1061,13 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     """Noise source "device" and no per-step table given: the step's update launch draws what it needs."""
     return self._noise_source == "device" and noises is None and q_noises is None
 
-  def _sample_loop(self, num_steps, reset, step, gkey, record, slot="_graph"):
+  def _sample_loop(self, num_steps, reset, step, gkey, record, slot="_graph", after_step=None):
     """Run `num_steps` DDIM steps from the state `reset()` sets (latents, U-Net input and the device counter at
     _loop_start_index(num_steps)); `step(dec_index)` enqueues one step.  With graphs (and no `record`) one step
     is captured once per `gkey` -- after a warm-up step on a side stream has allocated every scratch buffer --
     and replayed num_steps times; the counter lives on the device, so the graph serves any start index.  `slot`: the
-    attribute that keeps the graph (its key in `slot`_key): a loop with a slot of its own does not evict the others'."""
+    attribute that keeps the graph (its key in `slot`_key): a loop with a slot of its own does not evict the others'.
+    `after_step(s)` runs on the host after the s-th step is enqueued."""
     reset()
     use_graph = self._use_graph and record is None
     t0 = torch.cuda.Event(enable_timing=True)
@@ -935,41 +1092,73 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
         reset()
       graph = getattr(self, slot)
       t0.record()
-      for _ in range(num_steps):                                          # :484-502
+      for i in range(num_steps):                                          # :484-502
         graph.replay()
+        if after_step is not None:
+          after_step(i)
       t1.record()
     else:
       t0.record()
-      for _ in range(num_steps):
+      for i in range(num_steps):
         step(True)
         if record is not None:
           record.append(self._xt.clone())
+        if after_step is not None:
+          after_step(i)
       t1.record()
     self._loop_events = (t0, t1, num_steps)
 
-  def _denoise(self, k, set_start, guidance_scale, gsched, noise_table, masked, rng, record, decode=True):
+  def _denoise(self, k, set_start, guidance_scale, gsched, noise_table, masked, rng, record, decode=True,
+               preview_freq=None, on_preview=None):
     """DDIM indices k-1 .. 0 of the configured solver from the latents `set_start()` leaves in _xt / _x2 (what
     ddim_p_sample_loop, its start_index= form and the img2img loop share); returns the decoded images, or with
-    decode=False the latents (_xt itself: the current shape's state)."""
+    decode=False the latents (_xt itself: the current shape's state).  `preview_freq` = q:
+    every step also writes pred_x0 and ends with the one preview launch, captured with it in a graph slot of the
+    previews' own; None leaves the keys, the launches and the graphs as they are without the keyword."""
+    q = self._preview_on(preview_freq, on_preview, len(self._ddim_steps))
+
     def reset():
       set_start()
       self._index_dev.fill_(self._loop_start_index(k))                    # :476 (index = k - 1 in the first step)
       self._set_loop_start(k - 1)
+      if q is not None:                        # (outside the graph: what the warm-up and capture steps wrote goes,
+        self._pv_a.zero_()                     # and the slots this loop never reaches read 0)
+        self._pv_b.zero_()
+
+    def after_step(s):
+      index = k - 1 - s
+      if on_preview is not None and index % q == 0:
+        on_preview(index, self._pv_a[index // q], self._pv_b[index // q])
+
+    # previews: the update also writes pred_x0, one launch follows it, the key says so and the graphs have their slots
+    pv, pkey, own, own_sched = {}, (), {}, {}
+    if q is not None:
+      pv, pkey = dict(pred_x0_out=self._pv_x0), (("preview", q, self._pv_scale, self._pv_mode),)
+      own, own_sched = dict(slot="_pv_graph", after_step=after_step), dict(slot="_pv_sched", after_step=after_step)
+      self._pv_last = (q, k, self._pv_a, self._pv_b)
+
+    def step_sched(guided, dec):
+      self._step_sched(guided, dec, masked=masked, rng=rng, **pv)
+      if q is not None:
+        self._preview_step(q, dec)
+
+    def step(dec):
+      self._step(guidance_scale, False, noise_table, dec_index=dec, masked=masked, rng=rng, **pv)
+      if q is not None:
+        self._preview_step(q, dec)
 
     if gsched is not None:
-      self._sample_loop_sched(self._sched_forms(gsched, k - 1, k), reset,
-                              lambda guided, dec: self._step_sched(guided, dec, masked=masked, rng=rng),
-                              self._sched_key_of(masked, rng), record)
+      self._sample_loop_sched(self._sched_forms(gsched, k - 1, k), reset, step_sched,
+                              self._sched_key_of(masked, rng) + pkey, record, **own_sched)
       return self._finish(self._xt) if decode else self._xt
     gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, masked, self._noise_source, rng,
-            self._step_spacing, self._sampler)
-    self._sample_loop(k, reset, lambda dec: self._step(guidance_scale, False, noise_table, dec_index=dec,
-                                                        masked=masked, rng=rng), gkey, record)
+            self._step_spacing, self._sampler) + pkey
+    self._sample_loop(k, reset, step, gkey, record, **own)
     return self._finish(self._xt) if decode else self._xt
 
   def ddim_p_sample_loop(self, cond_model_inputs, shape, guidance_scale=5., x_T=None,
                          noises=None, seed=0, first_sample_index=0, record=None, guidance_interval=None,
-                         start_index=None):
+                         start_index=None, preview_freq=None, on_preview=None):
     """model_runners.py:474-509.  Extra inputs the reference lacks: `x_T` [B,h,w,4]
     (else N(0,1) from `seed`, keyed per global sample index), `noises` [N,B,h,w,4]
     indexed by DDIM index (only read when eta > 0), `record` (list: receives x_t
@@ -979,7 +1168,12 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     training timesteps (guided where t_lo <= steps[i] <= t_hi); DESIGN.md section 11, eta = 0 only.
     `start_index` = k in [1, N]: `x_T` (required) lies on the level of steps[k-1], what
     ddim_invert_loop returns, and the loop runs DDIM indices k-1 .. 0 only, a multistep solver without history at
-    its first step; tables and schedules stay indexed by DDIM index.  None: all N steps."""
+    its first step; tables and schedules stay indexed by DDIM index.  None: all N steps.
+    `preview_freq` = q (needs set_preview or fit_preview): every step also writes small RGB
+    pictures of x_t and of its predicted x_0 into slot index / q of two uint8 strips when its DDIM index is a multiple
+    of q, with one extra launch inside the captured step; last_previews() returns the strips, and
+    `on_preview(ddim_index, sample_u8, pred_x0_u8)` is called on the host after each such step is enqueued with device
+    views [B,H,W,3] of its slot (nothing synchronises unless the callback reads them).  None: nothing changes."""
     gsched = self._guidance(guidance_scale, guidance_interval)
     n = len(self._ddim_steps)
     k = n
@@ -990,10 +1184,11 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       if k != start_index or not 1 <= k <= n:
         raise ValueError(f"start_index must be an int in [1, {n}], got {start_index!r}")
     context = self._cond_stage_model(cond_model_inputs)                   # :475
-    return self._sample_from(context, shape, k, guidance_scale, gsched, x_T, noises, seed, first_sample_index, record)
+    return self._sample_from(context, shape, k, guidance_scale, gsched, x_T, noises, seed, first_sample_index, record,
+                             preview_freq=preview_freq, on_preview=on_preview)
 
   def _sample_from(self, context, shape, k, guidance_scale, gsched, x_T, noises, seed, first_sample_index, record,
-                   decode=True):
+                   decode=True, preview_freq=None, on_preview=None):
     """ddim_p_sample_loop from the text context on: DDIM indices k-1 .. 0 from x_T."""
     B, h, w, c = (int(s) for s in shape)
     xt = self._x_T(x_T, seed, first_sample_index, B, h, w, c)
@@ -1004,7 +1199,8 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     rng = self._draws_on_device(noises)
     noise_table = None if rng else self._eta_noise_table(noises, seed, first_sample_index, B, h, w, c)
     return self._denoise(k, lambda: self._set_x_T(xt, seed, first_sample_index, B), guidance_scale, gsched,
-                         noise_table, False, rng, record, decode=decode)
+                         noise_table, False, rng, record, decode=decode, preview_freq=preview_freq,
+                         on_preview=on_preview)
 
   def _x_T(self, x_T, seed, first_sample_index, B, h, w, c):
     """The caller's x_T on the device; drawn on the host when omitted; None (noise source "device") = drawn on the
@@ -1044,7 +1240,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
   def ddim_p_sample_loop_img2img(self, cond_model_inputs, init_images, guidance_scale=5., strength=0.75,
                                  mask=None, encode_noise=None, q_noises=None, noises=None, seed=0,
                                  first_sample_index=0, record=None, guidance_interval=None, image_size=None,
-                                 fit="stretch", resample="lanczos3"):
+                                 fit="stretch", resample="lanczos3", preview_freq=None, on_preview=None):
     """img2img (SDEdit) and masked inpainting on the DDIM loop.
     cond_model_inputs: token ids [uncond x B; cond x B].  init_images [B,H,W,3] (or [H,W,3], tiled) float32
     in [-1, 1].  z0 = get_latents(init_images, encode_noise); k = int(strength * N); the loop starts from
@@ -1058,8 +1254,9 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     "crop" its centred box of the target's aspect ratio (resample.crop_box), `resample` names the filter of
     ops.resample_nhwc; images already (H, W) take the path above untouched -- and `mask` may also be a pixel mask at the
     source images' size ([B,Hs,Ws] or [Hs,Ws], nonzero = keep), reduced over the same box by latent_mask_fit; a mask
-    whose extents are the latent ones is read as a latent mask.  Returns the decoded images; the final latents stay
-    in self._xt."""
+    whose extents are the latent ones is read as a latent mask.  `preview_freq` / `on_preview` as in
+    ddim_p_sample_loop (the strips have a slot for every multiple of q below N; the loop writes those it reaches, up
+    to (k-1) // q, and leaves the others 0).  Returns the decoded images; the final latents stay in self._xt."""
     size = self._image_size(image_size, fit, resample)
     gsched = self._guidance(guidance_scale, guidance_interval)
     n = len(self._ddim_steps)
@@ -1077,9 +1274,10 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     context = self._cond_stage_model(cond_model_inputs)
     z0 = self.get_latents(imgs, noise=encode_noise, seed=seed, first_sample_index=first_sample_index)
     return self._sdedit(context, z0, k, guidance_scale, gsched, mask, q_noises, noises, seed, first_sample_index,
-                        record)
+                        record, preview_freq=preview_freq, on_preview=on_preview)
 
-  def _sdedit(self, context, z0, k, guidance_scale, gsched, mask, q_noises, noises, seed, first_sample_index, record):
+  def _sdedit(self, context, z0, k, guidance_scale, gsched, mask, q_noises, noises, seed, first_sample_index, record,
+              preview_freq=None, on_preview=None):
     """The img2img loop from the latents z0 [B,h,w,c] on: q_sample to the level of steps[k-1], DDIM indices k-1 .. 0
     (with the blend when `mask` is given), decode."""
     n = len(self._ddim_steps)
@@ -1116,7 +1314,8 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       else:
         ops.q_sample(z0_buf, q_buf[k - 1], t_start, sa, sb, self._xt, x_unet_out=self._x2)
 
-    return self._denoise(k, set_start, guidance_scale, gsched, noise_table, masked, rng, record)
+    return self._denoise(k, set_start, guidance_scale, gsched, noise_table, masked, rng, record,
+                         preview_freq=preview_freq, on_preview=on_preview)
 
   # ---- two-pass high-resolution sampling --------------------------------
   def ddim_p_sample_loop_hires(self, cond_model_inputs, shape, hires_shape, strength=0.5, resize="bilinear",

@@ -21,7 +21,7 @@ __all__ = [
     "bmm_nt", "conv3x3_small", "groupnorm", "layernorm", "softmax_rows", "attention",
     "time_embedding", "gemv", "cfg_ddim_update", "cfg_ddim_update_masked", "cfg_plms_update", "q_sample",
     "philox_u32", "normal_fill", "q_sample_rng", "cfg_ddim_update_rng", "cfg_plms_update_rng", "cfg_ms_update",
-    "cfg_ms_update_rng", "cfg_sched_update", "cfg_ddim_invert_update", "window_gather", "window_fold", "window_gather_ex", "window_fold_ex", "wrap_pad", "resize_nhwc", "resample_nhwc", "post_quant", "vq_nearest", "embedding",
+    "cfg_ms_update_rng", "cfg_sched_update", "cfg_ddim_invert_update", "window_gather", "window_fold", "window_gather_ex", "window_fold_ex", "wrap_pad", "resize_nhwc", "resample_nhwc", "latent_preview", "post_quant", "vq_nearest", "embedding",
     "minmax_u8", "cast",
 ]
 
@@ -1169,6 +1169,39 @@ def resample_nhwc(x, size, filter="lanczos3", out=None):
   check(lib.ldm_resample_nhwc(_ptr(_f32(x, "x")), _ptr(tmp), _ptr(_f32(out, "out")), B, H, W, c, Ho, Wo, _ptr(xs),
                               _ptr(xw), xt, _ptr(ys), _ptr(yw), yt, _stream()), "ldm_resample_nhwc")
   return out
+
+
+def latent_preview(lat_a, proj, frames_a, freq, index=None, index_bias=0, lat_b=None, frames_b=None, scale=1,
+                   mode="bilinear"):
+  """Latent previews (include/ldm_hip.h): lat_a (and lat_b) [B,h,w,c] float32 -> RGB bytes in
+  slot r of frames_a (frames_b) [R,B,s*h,s*w,3] uint8, s = `scale`, through proj [c+1,3] float32 (c weight rows, then
+  the bias), an upscale (`mode` "nearest" or "bilinear"; an int is handed to the launcher as it is) and the 8-bit
+  quantisation.  r = idx / freq for idx = index[0] + index_bias (`index` a device int32 tensor, None = 0) when idx is
+  a non-negative multiple of `freq` and r < R; any other idx writes nothing.  The frames may start at any byte."""
+  if isinstance(mode, str):
+    if mode not in _lib.PREVIEW_MODES:
+      raise ValueError(f"preview mode must be one of {tuple(_lib.PREVIEW_MODES)}, got {mode!r}")
+    mode = _lib.PREVIEW_MODES[mode]
+  assert lat_a.dim() == 4 and lat_a.is_contiguous(), (tuple(lat_a.shape), lat_a.stride())
+  B, h, w, c = (int(v) for v in lat_a.shape)
+  scale = int(scale)
+  assert proj.is_contiguous() and tuple(proj.shape) == (c + 1, 3), (tuple(proj.shape), (c + 1, 3))
+  assert frames_a.dim() == 5, tuple(frames_a.shape)
+  R = int(frames_a.shape[0])
+  shape = (R, B, scale * h, scale * w, 3)
+  for lat, frames in ((lat_a, frames_a), (lat_b, frames_b)):
+    if frames is not None:
+      assert frames.dtype == torch.uint8 and frames.is_contiguous(), (frames.dtype, frames.stride())
+      if 1 <= scale <= 16:
+        assert tuple(frames.shape) == shape, (tuple(frames.shape), shape)
+    if lat is not None:
+      assert lat.is_contiguous() and tuple(lat.shape) == (B, h, w, c), (tuple(lat.shape), (B, h, w, c))
+  if index is not None:
+    assert index.dtype == torch.int32 and index.numel() >= 1
+  check(lib.ldm_latent_preview(_ptr(_f32(lat_a, "lat_a")), _ptr(_f32(lat_b, "lat_b")), _ptr(_f32(proj, "proj")),
+                               _ptr(frames_a), _ptr(frames_b), _ptr(index), int(index_bias), int(freq), R, B, h, w,
+                               c, scale, int(mode), _stream()), "ldm_latent_preview")
+  return frames_a
 
 
 def post_quant(latents, scale_factor, kernel_io, bias, out):

@@ -69,6 +69,16 @@ that size on the device) or `crop` (its centred box of that aspect ratio is), an
 own size.  Optional key `hires_pixel_filter` (the same three names; needs `hires_shape`): the two-pass loop enlarges
 in pixel space -- decode, resample, encode -- instead of resizing the latents, and the autoencoder is built with its
 encoder.  Without these keys nothing changes.
+
+Latent previews: optional `ldm_sampling` key `preview_freq: q` (an int of at least 1).  Every step
+whose DDIM index is a multiple of q also writes a small RGB picture of the current latents and of the predicted x_0 --
+an affine map of the latent channels to RGB, an upscale and an 8-bit quantisation, one extra launch inside the captured
+step -- and main() saves the two strips, uint8 [B,R,H,W,3], as `preview_sample.npy` and `preview_x0.npy` beside `--out`.
+`preview_scale` (default: the autoencoder's downsampling factor, so a preview has the image's size), `preview_mode`
+(`nearest` or `bilinear`, the default) and `preview_matrix` (a .npy of float32 [c+1,3]: c weight rows, then the bias;
+default: fitted on the decoder with a few noise latents, which is rough -- tools/fit_preview.py fits one on a run's
+latents) each need `preview_freq`.  The txt2img and img2img loops take it; `window`, `hires_shape`, `source_prompt` and
+`sample_save_progress` cannot be combined with it.  Without `preview_freq` nothing changes.
 """
 from __future__ import annotations
 
@@ -83,8 +93,8 @@ import yaml
 from . import ops
 from .autoencoder import AutoencoderKL, AutoencoderVQ
 from ._lib import RESAMPLE_FILTERS
-from .model_runners import (FITS, RESIZE_MODES, WINDOW_WEIGHTS, LatentDiffusionModelSampler, latent_mask,
-                            window_and_stride)
+from .model_runners import (FITS, PREVIEW_MODES, RESIZE_MODES, WINDOW_WEIGHTS, LatentDiffusionModelSampler,
+                            latent_mask, window_and_stride)
 from .tokenizer import get_token_ids
 from .transformer import TransformerModel
 from .unet import UNet
@@ -289,12 +299,66 @@ def edit_call(config, token_ids, source_ids, seed):
   return "ddim_p_sample_loop_edit", (source_ids, token_ids, _init_images(samp), samp["guidance_scale"]), kwargs
 
 
+PREVIEW_KEYS = ("preview_scale", "preview_mode", "preview_matrix")
+
+
+def preview_settings(config):
+  """`ldm_sampling.preview_freq` with `preview_scale` / `preview_mode` / `preview_matrix` (the
+  reference's YAML has no such keys), checked: None without `preview_freq`, else dict(freq=, scale=, mode=, matrix=
+  the .npy's path or None).  The previews belong to the txt2img and img2img loops."""
+  samp = config["ldm_sampling"]
+  q = samp.get("preview_freq")
+  if q is None:
+    for key in PREVIEW_KEYS:
+      if samp.get(key) is not None:
+        raise ValueError(f"ldm_sampling.{key} needs ldm_sampling.preview_freq")
+    return None
+  if isinstance(q, bool) or not isinstance(q, int) or q < 1:
+    raise ValueError(f"ldm_sampling.preview_freq must be an int of at least 1, got {q!r}")
+  for key in ("window", "hires_shape", "source_prompt", "sample_save_progress"):
+    if samp.get(key) is not None and samp.get(key) is not False:
+      raise ValueError(f"ldm_sampling.preview_freq cannot be combined with ldm_sampling.{key}")
+  scale = samp.get("preview_scale", downsampling_factor(config))
+  if isinstance(scale, bool) or not isinstance(scale, int) or not 1 <= scale <= 16:
+    raise ValueError(f"ldm_sampling.preview_scale must be an int in [1, 16], got {scale!r}")
+  mode = samp.get("preview_mode", "bilinear")
+  if mode not in PREVIEW_MODES:
+    raise ValueError(f"ldm_sampling.preview_mode must be one of {PREVIEW_MODES}, got {mode!r}")
+  matrix = samp.get("preview_matrix")
+  if matrix is not None and not isinstance(matrix, str):
+    raise ValueError(f"ldm_sampling.preview_matrix must be the path of a .npy, got {matrix!r}")
+  return dict(freq=q, scale=scale, mode=mode, matrix=matrix)
+
+
+def preview_kwargs(config):
+  """The loops' keyword of `ldm_sampling.preview_freq`: nothing when the key is absent."""
+  pv = preview_settings(config)
+  return {} if pv is None else dict(preview_freq=pv["freq"])
+
+
+def setup_preview(sampler, config, seed):
+  """Hands the sampler the previews' matrix, scale and mode before the loop: `preview_matrix`'s .npy, else a matrix
+  fitted on the decoder at `latent_shape` (fit_preview).  Nothing without `preview_freq`."""
+  pv = preview_settings(config)
+  if pv is None:
+    return
+  if pv["matrix"] is not None:
+    proj = np.load(pv["matrix"])
+    c = config["ldm_sampling"]["latent_shape"][3]
+    if proj.dtype != np.float32 or proj.shape != (c + 1, 3):
+      raise ValueError(f"preview_matrix must be float32 [{c + 1},3], got {proj.dtype} {proj.shape}")
+  else:
+    proj = sampler.fit_preview(seed=seed, shape=config["ldm_sampling"]["latent_shape"][1:])
+  sampler.set_preview(proj, scale=pv["scale"], mode=pv["mode"])
+
+
 def sampling_call(config, token_ids, seed, source_ids=None):
   """(sampler method name, positional args, kwargs) of the call main() makes for `config`.  `source_ids`: the token
   ids of `ldm_sampling.source_prompt` when the key is there."""
   samp = config["ldm_sampling"]
   base = (token_ids, samp["latent_shape"], samp["guidance_scale"])
   init_fit_kwargs(config)                        # (ValueError: an unknown init_fit or init_filter, whatever the loop)
+  preview = preview_kwargs(config)               # (ValueError: a loop without previews, or a key without preview_freq)
   for key in PANORAMA_WRAP_KEYS:
     if samp.get(key) is not None and samp.get("window") is None:
       raise ValueError(f"ldm_sampling.{key} needs ldm_sampling.window")
@@ -313,7 +377,7 @@ def sampling_call(config, token_ids, seed, source_ids=None):
       raise ValueError("sample_save_progress is not supported with init_image")
     images = _init_images(samp)
     fit = init_fit_kwargs(config)
-    kwargs = dict(strength=float(samp.get("strength", 0.75)), seed=seed, **guidance_kwargs(config), **fit)
+    kwargs = dict(strength=float(samp.get("strength", 0.75)), seed=seed, **guidance_kwargs(config), **fit, **preview)
     if samp.get("mask") is not None:
       pm = np.load(samp["mask"])
       if fit:
@@ -324,7 +388,7 @@ def sampling_call(config, token_ids, seed, source_ids=None):
     return "ddim_p_sample_loop_img2img", (token_ids, images, samp["guidance_scale"]), kwargs
   if samp.get("sample_save_progress"):
     return "ddim_p_sample_loop_progressive", base, dict(seed=seed, **guidance_kwargs(config))
-  return "ddim_p_sample_loop", base, dict(seed=seed, **guidance_kwargs(config))
+  return "ddim_p_sample_loop", base, dict(seed=seed, **guidance_kwargs(config), **preview)
 
 
 def build_from_config(config, dtype=torch.bfloat16, device="cuda:0", seed=2, use_graph=True,
@@ -399,9 +463,16 @@ def main(argv=None):
       u8 = tensor_to_image(t.reshape(b, r * t.shape[2], t.shape[3], t.shape[4]))
       np.save(name, u8.reshape(tuple(t.shape)))
     return
+  setup_preview(sampler, config, args.seed)
   images = getattr(sampler, method)(*args_, **kwargs)
   print(f"[INFO] Save generated images to '{args.out}'...")
   np.save(args.out, tensor_to_image(images))
+  if "preview_freq" in kwargs:
+    strips = sampler.last_previews()
+    for name, key in (("preview_sample.npy", "sample"), ("preview_x0.npy", "pred_x0")):
+      path = os.path.join(os.path.dirname(os.path.abspath(args.out)), name)
+      print(f"[INFO] Save latent previews to '{path}'...")
+      np.save(path, strips[key])
 
 
 if __name__ == "__main__":
