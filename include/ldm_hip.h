@@ -51,7 +51,13 @@ extern "C" {
 #define LDM_ACT_NONE 0
 #define LDM_ACT_GELU 1  /* exact erf gelu: transformer.py:169 (tf.nn.gelu)        */
 #define LDM_ACT_GEGLU 2 /* value*gelu(gate): unet.py:323-325; weight rows interleaved
-                           in blocks of 64 = 32 value rows then their 32 gate rows  */
+                           in blocks of 64 = 32 value rows then their 32 gate rows.
+                           Tiles 0 (auto), 1, 2, 5, 11, 12, 14, 19.  Takes no addend
+                           (LDM_ERR_ARG).  On tiles 11 / 12 without split-K the output
+                           must qualify for the 16-byte vector epilogue (out, bias and
+                           residual 16-byte aligned, row pitches multiples of 8
+                           elements), else LDM_ERR_ARG; the automatic plan (tile 0)
+                           does not pick them for such a call                      */
 #define LDM_ACT_SILU 3  /* unet.py:72 Dense(activation="silu")                     */
 
 int ldm_version(void);

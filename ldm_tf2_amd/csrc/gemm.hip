@@ -205,6 +205,19 @@ void launch_mode(int cfg, const GemmArgs& a, dim3 grid, hipStream_t s) {
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// vectorised epilogue: row-major output whose every 8-column piece is 16-byte addressable
+bool vec_epilogue_ok(const ldm_gemm_params* p) {
+  const int nout = p->act == LDM_ACT_GEGLU ? p->N / 2 : p->N;
+  auto al = [](const void* q, int by) { return ((uintptr_t)q % by) == 0; };
+  return p->ldc_n == 1 && nout % 8 == 0 && p->ldc_m % 8 == 0 && p->stride_c % 8 == 0 && al(p->out, 16) &&
+         (!p->residual || (p->ldr % 8 == 0 && p->stride_r % 8 == 0 && al(p->residual, 16))) &&
+         (!p->bias || al(p->bias, 16)) &&
+         (!p->addend || (al(p->addend, 16) && p->add_ld % 4 == 0));
+}
+// The 16x16x32 tiles apply GEGLU in the vector epilogue only (their accumulator blocks are 16 wide: the generic
+// epilogue's value block j / gate block j + 1 pairing does not exist there).  With split-K the reduce kernels apply it.
+constexpr bool geglu_needs_vec(int c) { return c == 11 || c == 12; }
+
 // Choose tile config + split-K jointly with a small cost model calibrated on MI355X
 // (tools/gemm_bench.py): a launch runs in rounds of (256 CUs x resident workgroups)
 // tiles; a round costs (K-tiles per split + a fixed prologue/epilogue overhead) x the
@@ -223,6 +236,7 @@ void choose(const ldm_gemm_params* p, int esize, int* cfg_out, int* split_out) {
   const int bke = 128 / esize;
   const int ktiles = cdiv(p->K, bke);
   const bool geglu = p->act == LDM_ACT_GEGLU;
+  const bool geglu_vec = geglu && vec_epilogue_ok(p);
   const double f32x = esize == 4 ? 8.0 : 1.0;   // f32 MFMA: 1/16 the rate at half the K per tile
   double best = 1e30;
   int best_cfg = 2, best_split = 1;
@@ -244,6 +258,7 @@ void choose(const ldm_gemm_params* p, int esize, int* cfg_out, int* split_out) {
     for (int split : kSplits) {
       if (p->split_k > 0 && split != p->split_k) continue;
       if (is_persistent(c) && split > 1) continue;   // the persistent kernel does not split K
+      if (geglu && geglu_needs_vec(c) && split == 1 && !geglu_vec) continue;   // unsplit, it stores through the vector epilogue only
       // split-K only rescues launches that cannot fill the machine once, and must fit
       // the caller's workspace
       if (split > 1 && (p->batch != 1 || ktiles / split < 4 || tiles >= 256.0 * kResident[c] ||
@@ -321,14 +336,7 @@ void build_args(const ldm_gemm_params* p, int cfg, int split, int kps, GemmArgs*
     a.a2 = (const char*)p->a2; a.lda2 = p->lda2; a.kt9 = (p->K - p->Cin2) / bke;
     a.a2_bytes = (uint32_t)((((int64_t)p->M - 1) * p->lda2 + p->Cin2) * esize);
   }
-  // vectorised epilogue: row-major output whose every 8-column piece is 16-byte addressable
-  const int nout = p->act == LDM_ACT_GEGLU ? p->N / 2 : p->N;
-  auto al = [](const void* q, int by) { return ((uintptr_t)q % by) == 0; };
-  a.vec_epilogue =
-      p->ldc_n == 1 && nout % 8 == 0 && p->ldc_m % 8 == 0 && p->stride_c % 8 == 0 && al(p->out, 16) &&
-      (!p->residual || (p->ldr % 8 == 0 && p->stride_r % 8 == 0 && al(p->residual, 16))) &&
-      (!p->bias || al(p->bias, 16)) &&
-      (!p->addend || (al(p->addend, 16) && p->add_ld % 4 == 0));
+  a.vec_epilogue = vec_epilogue_ok(p);
   a.ktiles = cdiv(p->K, bke);
   a.split_k = split;
   a.ktiles_per_split = kps;
@@ -363,6 +371,7 @@ extern "C" int ldm_gemm_splits(const ldm_gemm_params* p) {
 
 extern "C" int ldm_gemm_reduce(const ldm_gemm_params* p, void* stream) {
   LDM_CHECK_ARG(p && p->out && p->workspace, "ldm_gemm_reduce: null pointer");
+  LDM_CHECK_ARG(!(p->act == LDM_ACT_GEGLU && p->addend), "ldm_gemm_reduce: GEGLU takes no addend");
   int cfg, split, kps;
   final_plan(p, &cfg, &split, &kps);
   LDM_CHECK_ARG(split > 1, "ldm_gemm_reduce: these parameters do not split K (nothing was deferred)");
@@ -453,6 +462,7 @@ extern "C" int ldm_gemm(const ldm_gemm_params* p, void* stream) {
   if (p->act == LDM_ACT_GEGLU) {
     LDM_CHECK_ARG(p->N % 64 == 0, "ldm_gemm: GEGLU needs N %% 64 == 0");
     LDM_CHECK_ARG(p->ldc_n == 1, "ldm_gemm: GEGLU needs a row-major output");
+    LDM_CHECK_ARG(!p->addend, "ldm_gemm: GEGLU takes no addend");
   }
   LDM_CHECK_ARG(p->ldc_n == 1 || p->ldc_m == 1, "ldm_gemm: one of ldc_m / ldc_n must be 1");
 
@@ -485,7 +495,10 @@ extern "C" int ldm_gemm(const ldm_gemm_params* p, void* stream) {
     LDM_CHECK_ARG(p->rows2 > 0 && p->rows2 % 4 == 0 && p->M % p->rows2 == 0 && p->ld2 % 4 == 0 && p->stride2 % 4 == 0 &&
                       ((uintptr_t)p->out2 % 16) == 0, "ldm_gemm: out2 geometry (rows2 %% 4, M %% rows2, ld2 / stride2 %% 4, alignment)");
   }
-  if (p->act == LDM_ACT_GEGLU) LDM_CHECK_ARG(cfg <= 2 || cfg == 5 || cfg == 11 || cfg == 12 || cfg == 14 || cfg == 19, "ldm_gemm: GEGLU needs a tile whose width is a multiple of 64 (1, 2, 5, 11, 12)");
+  if (p->act == LDM_ACT_GEGLU) LDM_CHECK_ARG(cfg <= 2 || cfg == 5 || cfg == 11 || cfg == 12 || cfg == 14 || cfg == 19, "ldm_gemm: GEGLU needs a tile whose width is a multiple of 64 (1, 2, 5, 11, 12, 14, 19)");
+  if (p->act == LDM_ACT_GEGLU && geglu_needs_vec(cfg) && split <= 1)
+    LDM_CHECK_ARG(vec_epilogue_ok(p), "ldm_gemm: GEGLU on tile %d without split-K needs the 16-byte alignment of the vector epilogue: "
+                  "out, bias and residual 16-byte aligned, row pitches multiples of 8 elements", cfg);
   LDM_CHECK_ARG(!kBf16Only[cfg] || esize == 2, "ldm_gemm: tile %d is bf16 only", cfg);
   if (p->conv && p->upsample == 2)
     LDM_CHECK_ARG(phase_tile_ok(cfg, esize), "ldm_gemm: tile %d has no phase form (upsample = 2): tiles 2, 9, 11 (bf16) / 1, 2 (f32)", cfg);

@@ -57,11 +57,29 @@ test in test_gemm_accounting_gpu.py; nothing is launched at such a size).
 
 First run on an MI355X: see RESULTS at the end of this docstring.
 
+ACTIVATION EPILOGUES (`epilogue_cases`, run by test_zz_gemm_epilogue_gpu.py, proven by test_gemm_epilogue_probes_cpu.py)
+  The cases above run with act = NONE.  An activation cannot keep integer outputs, so these cases make the value BEFORE
+  it exact instead: the selection probe with one phase, wt one-hot of value 2^-4 (a power of two in the weights, not in
+  alpha: the persistent tiles demand alpha == 1), A = `ecode` in +-31, bias / addend / residual = k 2^-4 with |k| <= 16.
+  Every z = a 2^-4 + bias + addend is a multiple of 2^-4 with |z| <= 3.94; on that grid one step moves GELU or SiLU by
+  at least 3.4e-5 up to |z| = 4.  LayerNorm fold: rows of +-1 in equal numbers and eps = 2^-30 give mean = 0 and
+  rstd = 1 exactly in float32 (the real-number rstd differs by 2^-31, a thousandth of the smallest ceiling), the weights
+  carry wv(n) 2^-4.  `reference_pre` is the exact z (`reference` without the residual), `reference_act` the float64
+  activation in the header's GEGLU layout (output column c pairs logical columns (c >> 5) 64 + (c & 31) and + 32) plus the
+  residual.  Gates: uniformity (exact), a derived ceiling per element (`ceiling`: float32 2e-6 for GELU / SiLU = A&S
+  7.1.26 at 1.5e-7 on erf, 3e-7 at |z| = 4, + exp2 / rcp at 1 ulp each + the output's rounding; a float32 emulation of
+  gelu_erf_f / silu_f with exact exp2 / rcp stays below 6e-7 on the grid; GEGLU |value| 2e-6 + 2^-23 |ref|; bf16 output
+  + 2^-8 |ref|) and a measured gate (GPU module).  `EPI_MUTATIONS`: each moves some element by more than 8 ceilings in
+  every case it applies to; exempt: geglu_* without GEGLU, geglu_gate_bias_missing / _addend_missing without that term,
+  act_before_bias and bias_column without bias and addend, residual_inside_act without residual, stored_width unless
+  GEGLU spans more than one n-tile.  The matrix: the docstring of test_zz_gemm_epilogue_gpu.py and `_epi_cases`.
+
 RESULTS
   every form of the matrix (tiles 0-19, both storage types where the tile has them, plain rows, the three convolution
   forms, the halo-staged tiles, split-K with both reduce kernels, the persistent tiles in both deals) passed both probes
   with equality when first run; no kernel was changed.  The host check of the upsampled form was tightened (above).
 """
+import math
 from collections import namedtuple
 
 import torch
@@ -113,8 +131,12 @@ def bke_of(form):
 
 _FIELDS = dict(form="", kind="plain", M=0, N=0, K=0, K2=0, B=0, H=0, W=0, Cin=0, stride=1, up=0, nlp=0,
                bias=0, addend=0, add_rows=0, res=0, alpha=1.0, odt=None, lda_x=0, ldc_x=0, ldr_x=0, lda2_x=0, off8=0,
-               split=1, defer=0, in_slice=0, out_slice=0, Bt=1, shared_w=0, trans=0, G=1, sel=0, tag="")
+               split=1, defer=0, in_slice=0, out_slice=0, Bt=1, shared_w=0, trans=0, G=1, sel=0, tag="",
+               act=0, boff=0, lnf=0, rej="")
 Case = namedtuple("Case", list(_FIELDS), defaults=list(_FIELDS.values()))
+# act: 0 | "gelu" | "silu" | "geglu" (the activation-epilogue matrix at the end of this module; all_cases() has none);
+# boff: the bias is a slice that starts 4 bytes behind a 16-byte boundary; lnf: LayerNorm fold (ops.linear(ln_fold=));
+# rej: the launch must be rejected with a message that matches this pattern
 # kind: plain (ops.linear) | conv (ops.conv3x3) | bmm (ops.bmm_nt) | lint (ops.linear_t) | out2 (ops.linear(out2=))
 #   out2: columns [0, N - K2x) row-major, the rest transposed per group of M / G rows; `G` groups (lint too)
 # lda_x / ldc_x / ldr_x / lda2_x: extra elements in the row pitch of a / out / residual / a2; off8: out starts 8 bytes
@@ -692,3 +714,297 @@ def all_cases():
     ids = [case_id(c) for c in _ALL]
     assert len(set(ids)) == len(ids), [i for i in ids if ids.count(i) > 1][:4]
   return _ALL
+
+
+# ===========================================================================================================
+# Activation epilogues: act(alpha sum + bias + addend) + residual on every store path (module docstring, "ACTIVATION
+# EPILOGUES"; run by test_zz_gemm_epilogue_gpu.py, proven on the CPU by test_gemm_epilogue_probes_cpu.py)
+# ===========================================================================================================
+EPI_SCALE = 2.0 ** -4
+ACT_CODES = {0: 0, "gelu": 1, "geglu": 2, "silu": 3}                 # include/ldm_hip.h LDM_ACT_*
+ALIGN_REJ, ADDEND_REJ = "needs the 16-byte alignment", "GEGLU takes no addend"
+EPI_MUTATIONS = ("geglu_pair_shift", "geglu_blocks_swapped", "geglu_gate_bias_missing", "geglu_gate_addend_missing",
+                 "act_before_bias", "residual_inside_act", "bias_column", "stored_width", "nothing_stored")
+CEIL_F32 = 2e-6                                                      # module docstring: how it is made up
+MUTATION_FACTOR = 8.0
+
+
+def nout_of(c):
+  return c.N // 2 if c.act == "geglu" else c.N
+
+
+def ecode(p, ch):
+  """The position code of the epilogue probe: non-zero, in [-31, 31] (31 prime), so that code * 2^-4 + bias + addend
+  stays within [-4, 4]."""
+  mag = 1 + (37 * p + 11 * ch) % 31
+  return torch.where((p + ch // 8) % 3 == 0, -mag, mag)
+
+
+def probe_epilogue(c):
+  """float64 operands, all multiples of 2^-4 that the storage types hold exactly.  wt[n, :] is one-hot at
+  selected_column(c, 0) with the value 2^-4 (LayerNorm fold: wv(n) 2^-4), A is `ecode` (LayerNorm fold: rows of +-1 in
+  equal numbers, so that mean = 0, E[x^2] = 1 and, with eps = 2^-30, rstd = 1 in float32), bias / addend / residual are
+  k 2^-4 with |k| <= 16: z = a[m, k(n)] w + bias[n] + addend[m / add_rows, n] is a multiple of 2^-4 with |z| <= 3.94."""
+  s, n = EPI_SCALE, torch.arange(c.N)
+  d = {}
+  if c.kind == "conv":
+    p = torch.arange(c.B * c.H * c.W).view(c.B, c.H, c.W, 1)
+    d["a"] = ecode(p, torch.arange(c.Cin).view(1, 1, 1, c.Cin)).to(F64)
+  elif c.lnf:
+    d["a"] = (1 - 2 * ((torch.arange(c.M).view(1, c.M, 1) + torch.arange(c.K).view(1, 1, c.K)) % 2)).to(F64)
+  else:
+    d["a"] = ecode(torch.arange(c.M).view(1, c.M, 1), torch.arange(c.K).view(1, 1, c.K)).to(F64)
+  wv = (1 + (7 * n) % 31) if c.lnf else torch.ones_like(n)
+  w = torch.zeros(1, c.N, c.K, dtype=F64)
+  w[0, n, selected_column(c, 0)] = wv.to(F64) * s
+  d["w"] = w
+  if c.bias:
+    d["bias"] = ((5 * n + 3) % 33 - 16).to(F64) * s
+  if c.addend:
+    g = torch.arange(-(-c.M // c.add_rows)).view(-1, 1)
+    d["addend"] = ((7 * n.view(1, -1) + 11 * g + 5) % 33 - 16).to(F64) * s
+  if c.res:
+    m, q = torch.arange(c.M).view(-1, 1), torch.arange(nout_of(c) + c.ldr_x).view(1, -1)
+    d["res"] = ((3 * m + 13 * q + 1) % 33 - 16).to(F64) * s          # the whole buffer, pad columns included
+  if c.lnf:
+    d["cs"] = w[0].sum(1)
+    d["eps"] = 2.0 ** -30
+  return d
+
+
+def gelu64(x):
+  return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
+
+
+def silu64(x):
+  return x / (1.0 + torch.exp(-x))
+
+
+def geglu_cols(c):
+  """(value, gate) logical columns of every output column: include/ldm_hip.h, blocks of 64 = 32 value rows, 32 gate rows."""
+  cc = torch.arange(c.N // 2)
+  nv = (cc >> 5) * 64 + (cc & 31)
+  return nv, nv + 32
+
+
+def reference_pre(c, d, mut=None):
+  """[Bt, M, N] float64: the exact pre-activation value z of every logical column (`reference` without the residual)."""
+  return reference(c._replace(res=0), d, mut)
+
+
+def _epi_terms(c, d):
+  """[M, N]: bias + addend alone."""
+  e = torch.zeros(c.M, c.N, dtype=F64)
+  if c.bias:
+    e = e + d["bias"]
+  if c.addend:
+    e = e + d["addend"][torch.arange(c.M) // c.add_rows]
+  return e
+
+
+def reference_act(c, d, mut=None):
+  """[Bt, M, nout] float64: act(z) + residual in float64 (GELU by erf, SiLU, value * gelu(gate) in the header's layout).
+  `mut`: one of EPI_MUTATIONS, the result of a subtly wrong epilogue."""
+  z = reference_pre(c, d, "bias_column" if mut == "bias_column" else None)
+  epi = _epi_terms(c, d)
+  res = d["res"][:, :nout_of(c)] if c.res else None
+  inside = mut == "residual_inside_act"
+  if c.act == "geglu":
+    nv, ng = geglu_cols(c)
+    if mut == "geglu_pair_shift":
+      ng = (ng + 1) % c.N
+    if mut == "geglu_blocks_swapped":
+      nv, ng = ng, nv
+    v, g = z[..., nv], z[..., ng]
+    if mut == "geglu_gate_bias_missing":
+      g = g - d["bias"][ng]
+    if mut == "geglu_gate_addend_missing":
+      g = g - d["addend"][torch.arange(c.M) // c.add_rows][:, ng]
+    if mut == "act_before_bias":
+      out = (v - epi[:, nv]) * gelu64(g - epi[:, ng]) + epi[:, nv]
+    else:
+      out = ((v + res) if inside else v) * gelu64(g)
+  else:
+    f = gelu64 if c.act == "gelu" else silu64
+    out = f(z - epi) + epi if mut == "act_before_bias" else f(z + res) if inside else f(z)
+  if res is not None and not inside:
+    out = out + res
+  if mut == "stored_width":                       # output column of n-tile ti computed from ti bn instead of ti bn / 2
+    bo = tile_of(FORMS[c.form]).bn // 2
+    cc = torch.arange(c.N // 2)
+    dest = (cc // bo) * 2 * bo + cc % bo
+    moved = torch.full_like(out, float("nan"))
+    moved[..., dest[dest < c.N // 2]] = out[..., cc[dest < c.N // 2]]
+    out = moved
+  if mut == "nothing_stored":
+    out = torch.full_like(out, float("nan"))
+  return out
+
+
+def epi_mutation_applies(c, kind):
+  if kind.startswith("geglu") and c.act != "geglu":
+    return False
+  if kind == "geglu_gate_bias_missing":
+    return bool(c.bias)
+  if kind == "geglu_gate_addend_missing":
+    return bool(c.addend)
+  if kind in ("act_before_bias", "bias_column"):
+    return bool(c.bias or c.addend)
+  if kind == "residual_inside_act":
+    return bool(c.res)
+  if kind == "stored_width":
+    return c.act == "geglu" and c.N > tile_of(FORMS[c.form]).bn
+  return True
+
+
+def ceiling(c, d, ref=None):
+  """[Bt, M, nout]: the derived bound of |out - reference_act| per element (module docstring).  `ref`: a mutated
+  reference to build the bound around instead (the failure report)."""
+  ref = reference_act(c, d) if ref is None else torch.nan_to_num(ref, nan=0.0)
+  if c.act == "geglu":
+    ce = reference_pre(c, d)[..., geglu_cols(c)[0]].abs() * CEIL_F32 + 2.0 ** -23 * ref.abs()
+  else:
+    ce = torch.full_like(ref, CEIL_F32)
+  return ce + 2.0 ** -8 * ref.abs() if c.odt == BF else ce
+
+
+def oracle_act(c, d, O):
+  """The same epilogue by oracle.ldm_oracle's gelu / silu in float32 on the exact z, rounded to the output type."""
+  z = reference_pre(c, d).to(F32)
+  if c.act == "geglu":
+    nv, ng = geglu_cols(c)
+    out = z[..., nv] * O.gelu(z[..., ng])
+  else:
+    out = O.gelu(z) if c.act == "gelu" else O.silu(z)
+  if c.res:
+    out = out + d["res"][:, :nout_of(c)].to(F32)
+  return out.to(c.odt).to(F64)
+
+
+def uniformity_groups(c, d):
+  """[Bt * M * nout] int64: outputs with the same number share (z, residual), for GEGLU (value, gate, residual)."""
+  z = reference_pre(c, d)
+  if c.act == "geglu":
+    nv, ng = geglu_cols(c)
+    keys = [z[..., nv], z[..., ng]]
+  else:
+    keys = [z]
+  keys.append(d["res"][:, :nout_of(c)].expand_as(keys[0]) if c.res else torch.zeros_like(keys[0]))
+  flat = torch.stack([k.reshape(-1) for k in keys], 1)
+  return torch.unique(flat, dim=0, return_inverse=True)[1]
+
+
+def not_uniform(got, groups):
+  """The number of groups whose members do not all hold the same value (NaN counts as a value of its own)."""
+  v = torch.nan_to_num(got.reshape(-1), nan=1e300)
+  n = int(groups.max()) + 1
+  lo = torch.full((n,), float("inf"), dtype=F64).scatter_reduce(0, groups, v, "amin")
+  hi = torch.full((n,), -float("inf"), dtype=F64).scatter_reduce(0, groups, v, "amax")
+  return int((lo != hi).sum())
+
+
+def exceeds(got, ref, ce, factor=1.0):
+  """[...] bool: |got - ref| > factor * ceiling, a NaN on one side only counting as an infinite difference."""
+  diff = (got - ref).abs()
+  diff = torch.where(torch.isnan(got) != torch.isnan(ref), torch.full_like(diff, float("inf")), diff)
+  return torch.nan_to_num(diff, nan=0.0) > factor * ce
+
+
+def matching_mutations(c, d, got):
+  """The mutations whose reference `got` meets within the ceiling (the failure report names them)."""
+  refs = {k: reference_act(c, d, k) for k in EPI_MUTATIONS if epi_mutation_applies(c, k)}
+  return [k for k, r in refs.items() if not bool(exceeds(got, r, ceiling(c, d, r)).any())]
+
+
+def epi_id(c):
+  base = case_id(c._replace(tag="", off8=0, ldc_x=0, defer=0, split=1) if c.tag else c)       # the tag names the store path
+  return base + f"-{c.act}" + (f"-{c.tag}" if c.tag else "") + ("-ln" if c.lnf else "") + ("-rej" if c.rej else "")
+
+
+def epi_group(c):
+  """The case without its store path: the float32 outputs of one group's paths are compared with each other."""
+  return c._replace(off8=0, ldc_x=0, boff=0, split=1, defer=0, rej="", tag="")
+
+
+_EPI_TILES = (0, 1, 2, 3, 4, 6, 7, 8, 9, 10, 11, 12, 17, 18, 19)
+_GEGLU_TILES = (0, 1, 2, 5, 11, 12, 19)
+_EPI_TERMS = ((1, 0, 0), (1, 1, 0), (1, 0, 1))                                # (bias, addend, residual)
+_EPI_COMBOS = [(mi, ni, term, oi) for mi in (0, 1) for ni in (0, 1) for term in (0, 1, 2) for oi in (0, 1)]
+# store paths, in two groups that each share one (M, N, terms, output type): vector epilogue / generic / vector reduce
+# and generic (pitch) / generic (bias) / scalar reduce
+_EPI_PATHS = ((("vec", {}), ("off8", dict(off8=1)), ("sk2", dict(split=2))),
+              (("ldc4", dict(ldc_x=4)), ("boff", dict(boff=1)), ("sk2off8", dict(split=2, off8=1))))
+
+
+def _forms_of(tiles):
+  return [n for t in tiles for n in ((f"t{t}-bf16",) if TILES.get(t, AUTO_NOMINAL).bf16_only else (f"t{t}-bf16", f"t{t}-f32"))]
+
+
+def _epi_cases():
+  out, gi = [], 0
+  for act, tiles in (("gelu", _EPI_TILES), ("silu", _EPI_TILES), ("geglu", _GEGLU_TILES)):
+    wide = 64 if act == "geglu" else 8
+    for name in _forms_of(tiles):
+      f = FORMS[name]
+      t, bke = tile_of(f), bke_of(f)
+      for paths in _EPI_PATHS:
+        mi, ni, term, oi = _EPI_COMBOS[(7 * gi) % len(_EPI_COMBOS)]
+        gi += 1
+        b, a, r = _EPI_TERMS[term if act != "geglu" else (0, 2)[term % 2]]     # GEGLU takes no addend
+        M = (1, t.bm + 1)[mi]
+        kw = dict(M=M, N=(wide, t.bn + wide)[ni], K=2 * bke, bias=b, addend=a, add_rows=37 if a and M > 37 else 0, res=r,
+                  ldr_x=8 * r, odt=F32 if f.dt == F32 or oi else BF, act=act)
+        for tag, pkw in paths:
+          if pkw.get("split") and not f.tile:
+            continue                                                          # the cost model's pick: no forced split
+          rej = ALIGN_REJ if act == "geglu" and f.tile in (11, 12) and not pkw.get("split") and tag != "vec" else ""
+          out.append(_mk(name, tag=tag, rej=rej, **kw, **pkw))
+      if act == "geglu":                                                      # finding 2: rejected on every path
+        kw = dict(M=t.bm + 1, N=t.bn + 64, K=2 * bke, bias=1, addend=1, add_rows=37, act=act, rej=ADDEND_REJ)
+        out.append(_mk(name, tag="vec", **kw))
+        if f.tile == 2:
+          out += [_mk(name, tag="off8", off8=1, **kw), _mk(name, tag="sk2", split=2, **kw),
+                  _mk(name, tag="defer", split=2, defer=1, **kw)]
+  # the deferred reduce, then ops.finish
+  for act in ("gelu", "silu", "geglu"):
+    for name in ("t2-bf16", "t2-f32", "t11-bf16"):
+      t, bke = tile_of(FORMS[name]), bke_of(FORMS[name])
+      out.append(_mk(name, tag="defer", M=t.bm + 1, N=t.bn + (64 if act == "geglu" else 8), K=2 * bke, bias=1, res=1, ldr_x=8,
+                     split=2, defer=1, act=act))
+  # the transposed store (GemmParams built by the test): one 32x32 tile, one 16x16x32 tile
+  for name, act, M in (("t2-bf16", "gelu", 129), ("t2-f32", "silu", 129), ("t11-bf16", "gelu", 257), ("t11-bf16", "silu", 131)):
+    t, bke = tile_of(FORMS[name]), bke_of(FORMS[name])
+    out.append(_mk(name, "tstore", M=M, N=t.bn + 8, K=2 * bke, bias=1, act=act))
+  # one 3x3 convolution with SiLU
+  for name in ("t2-bf16", "t11-bf16"):
+    out.append(_mk(name, "conv", B=1, H=3, W=5, Cin=64, N=136, bias=1, res=1, act="silu"))
+  # the persistent tiles: bias + activation only (the kernels that are built), both deals
+  i = 0
+  for tile, acts in ((13, ("gelu", "silu")), (14, ("gelu", "silu", "geglu"))):
+    for deal in ("wg1", "deal"):
+      name = f"t{tile}-bf16-{deal}"
+      f = FORMS[name]
+      for act in acts:
+        out.append(_mk(name, M=(1, 257)[i % 2], N=TILES[tile].bn * (1 + (i // 2) % 2), K=128, bias=1, split=f.wg, act=act))
+        i += 1
+      if tile == 14:
+        out.append(_mk(name, M=(257, 1)[i % 2], N=256, K=128, bias=1, split=f.wg, act="geglu", lnf=1))
+  # rejections that launch nothing
+  out.append(_mk("t13-bf16-deal", M=33, N=160, K=128, act="gelu", rej="no kernel for this epilogue"))
+  out.append(_mk("t14-bf16-wg1", M=33, N=128, K=128, split=-1, act="silu", rej="no kernel for this epilogue"))
+  out.append(_mk("t14-bf16-deal", "conv", B=1, H=3, W=5, Cin=64, N=128, bias=1, act="silu", rej="no kernel for this epilogue"))
+  out.append(_mk("t3-bf16", M=33, N=64, K=128, bias=1, act="geglu", rej="GEGLU needs a tile"))
+  out.append(_mk("t9-bf16", M=33, N=320, K=128, bias=1, act="geglu", rej="GEGLU needs a tile"))
+  return out
+
+
+_EPI = None
+
+
+def epilogue_cases():
+  global _EPI
+  if _EPI is None:
+    _EPI = _epi_cases()
+    ids = [epi_id(c) for c in _EPI]
+    assert len(set(ids)) == len(ids), [i for i in ids if ids.count(i) > 1][:4]
+  return _EPI

@@ -80,14 +80,42 @@ def take(view, flat):
   return got
 
 
-def run(dev, c, d):
-  """The product of case `c` on data `d` as float64 [Bt, M, N]."""
+def bias_of(c, d, dev):
+  """The bias on the device; c.boff: a slice that starts 4 bytes behind a 16-byte boundary of a NaN-filled buffer."""
+  if not c.boff:
+    return d["bias"].to(F32).to(dev)
+  buf = torch.full((c.N + 8,), NAN, dtype=F32)
+  buf[1:1 + c.N] = d["bias"].to(F32)
+  return buf.to(dev)[1:1 + c.N]
+
+
+def run(dev, c, d, hold=None):
+  """The product of case `c` on data `d` as float64 [Bt, M, N] (N / 2 columns with GEGLU).  `hold`: a list that
+  receives (view, flat) of the output before the launch, for a caller that expects the launch to be rejected."""
   o, f = ops(), G.FORMS[c.form]
   dt, odt = f.dt, c.odt
   K1 = c.K - c.K2
   kw = {}
+  nout = G.nout_of(c)
   if c.bias:
-    kw["bias"] = d["bias"].to(F32).to(dev)
+    kw["bias"] = bias_of(c, d, dev)
+  if c.kind == "tstore":
+    # the transposed store under an activation: the C ABI permits it, ops.bmm_nt passes no act
+    from ldm_tf2_amd._lib import GemmParams
+    a = padded(d["a"][0], 0, dt, dev)
+    wd = put(d["w"][0], dt, dev).contiguous()
+    ldn = (c.M + 7) // 8 * 8 + 8
+    flat = torch.full((c.N, ldn), NAN, dtype=odt, device=dev)
+    if hold is not None:
+      hold.append((flat[:, :c.M], flat))
+    p = GemmParams()
+    p.a, p.w, p.out, p.bias = o._ptr(a), o._ptr(wd), o._ptr(flat), o._ptr(kw.get("bias"))
+    p.lda, p.ldc_m, p.ldc_n = a.stride(0), 1, ldn
+    p.M, p.N, p.K, p.batch = c.M, c.N, c.K, 1
+    p.act, p.dtype, p.out_dtype, p.alpha = G.ACT_CODES[c.act], o.code(dt), o.code(odt), c.alpha
+    p.tile = f.tile
+    o._gemm(p, dev)
+    return take(flat[:, :c.M], flat).t().reshape(1, c.M, c.N)
   w = d["w"]
   if c.kind == "bmm":
     ab = torch.full((c.Bt, c.M + 1, c.K), NAN, dtype=F64)
@@ -106,7 +134,7 @@ def run(dev, c, d):
   wd = put(w[0], dt, dev).contiguous()
   if c.addend:
     kw["addend"] = d["addend"].to(F32).to(dev)
-  res2d = put(d["res"], odt, dev)[:, :c.N] if c.res else None
+  res2d = put(d["res"], odt, dev)[:, :nout] if c.res else None
   x2 = padded(d["a2"], c.lda2_x, dt, dev) if c.K2 else None
   split = c.split if f.tile else 0
   if c.kind == "conv":
@@ -127,6 +155,14 @@ def run(dev, c, d):
       kw["residual"] = res2d.reshape(c.B, oh, ow, c.N)
     if c.K2:
       kw["x2"] = x2.view(c.B, oh, ow, c.K2)
+    if hold is not None:
+      hold.append((out, flat))
+    if c.act:                                                          # ops.conv3x3 passes no act: its parameters + act
+      p = o._conv_params(x, wd, out, kw.get("bias"), c.stride, bool(c.up), kw.get("addend"), kw.get("residual"), f.tile,
+                         split, bool(c.nlp))
+      p.act = G.ACT_CODES[c.act]
+      o._gemm(p, dev)
+      return take(out, flat).reshape(1, c.M, c.N)
     r = o.conv3x3(x, wd, out, stride=c.stride, upsample=bool(c.up), no_lead_pad=bool(c.nlp), tile=f.tile, split_k=split,
                   defer_reduce=bool(c.defer), **kw)
     if c.defer:
@@ -148,16 +184,22 @@ def run(dev, c, d):
     o.linear(x, wd, qk, out2=vt, tile=f.tile, split_k=split, **kw)
     g2 = take(vt[:, :, :T], vt).permute(0, 2, 1).reshape(c.M, c.N - ns)
     return torch.cat([take(qk, qflat), g2], 1).reshape(1, c.M, c.N)
-  out, flat = out_rows(c.M, c.N, c.ldc_x, c.off8, odt, dev)
+  out, flat = out_rows(c.M, nout, c.ldc_x, c.off8, odt, dev)
+  if hold is not None:
+    hold.append((out, flat))
   if c.res:
     kw["residual"] = res2d
   if c.addend:
     kw["add_rows"] = c.add_rows
+  if c.act:
+    kw["act"] = G.ACT_CODES[c.act]
+  if c.lnf:
+    kw["ln_fold"] = (d["cs"].to(F32).to(dev), d["eps"])
   r = o.linear(x, wd, out, alpha=c.alpha, tile=f.tile, split_k=split, x2=x2, defer_reduce=bool(c.defer), **kw)
   if c.defer:
     assert (r is not None) == (G.expected_slabs(c) > 1)
     o.finish(r)
-  return take(out, flat).reshape(1, c.M, c.N)
+  return take(out, flat).reshape(1, c.M, nout)
 
 
 def test_tile_table_matches_the_library(dev):
