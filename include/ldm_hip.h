@@ -690,6 +690,30 @@ int ldm_latent_preview(const float* lat_a, const float* lat_b, const float* proj
                        const int32_t* index, int index_bias, int freq, int R, int B, int h, int w, int c, int scale,
                        int mode, void* stream);
 
+/*
+ * Cross-attention heat maps: the head-averaged softmax probabilities of the queries q against
+ * the keys k, weighted and ADDED into acc, so that a captured sampling step can collect the maps the flash attention
+ * kernels keep in registers.
+ *   q [R][T][heads*sp] (row stride ldq, batch stride q_bs, elements), k [R][Tk][heads*sp] (ldk, k_bs), both `dtype`;
+ *   acc [R][T][Tk] float32, contiguous, read-modify-write; S = the true head size, sp = the padded head stride.
+ * Per (r, t), heads in ascending order: l[j] = log2_scale * sum_{d<S} q[r][t][h sp + d] k[r][j][h sp + d] (one fma
+ * chain over d ascending; the dims d in [S, sp) never enter it, whatever they hold -- the matrix-softmax layout keeps a
+ * 1 in k's dim 40), e[j] = exp2(l[j] - max_j l[j]), p[j] = e[j] * rcp(sum_j e[j]), hs[j] += p[j]; then
+ * acc[r][t][j] = fma(w, hs[j] * (1 / heads), acc[r][t][j]).  All float32, hardware exp2 and reciprocal.  A query
+ * projection already scaled into the exp2 domain passes log2_scale = 1, a plain one S^-1/2 log2(e).
+ * The weight: idx = (index ? *index : 0) + index_bias; w = step_w ? step_w[idx] : 1.  With step_w given, idx outside
+ * [0, n_w) or w == 0 makes the launch write nothing at all (acc stays bit for bit).  *index is only read.
+ * One wave owns 64 consecutive queries of a row, one lane per query and one thread per acc element: no atomics, the
+ * result is deterministic.  q is read with 16-byte loads where q, ldq and q_bs allow, else element by element; same
+ * values.  Nothing is allocated or synchronised.  LDM_ERR_ARG, nothing launched: a null q, k or acc; a shape outside
+ * ldm_xattn_map_supported (heads >= 1, 1 <= Tk <= 80, 1 <= S <= sp, sp one of 32/48/64/80/96/160, dtype float32 or
+ * bf16); R or T below 1; ldq or ldk below heads*sp; step_w with n_w below 1.
+ */
+int ldm_xattn_map_supported(int heads, int Tk, int S, int sp, int dtype);
+int ldm_xattn_map(const void* q, int64_t ldq, int64_t q_bs, const void* k, int64_t ldk, int64_t k_bs, float* acc, int R,
+                  int heads, int T, int Tk, int S, int sp, float log2_scale, int dtype, const float* step_w, int n_w,
+                  const int32_t* index, int index_bias, void* stream);
+
 /* decode_first_stage prologue (model_runners.py:426 + autoencoder.py:362,434):
  * out = Dense_{C->C}(latents / scale_factor), C <= 8; float32 in, out_dtype out. */
 int ldm_post_quant(const float* latents, float scale_factor, const float* kernel_io,

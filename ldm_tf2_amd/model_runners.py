@@ -371,6 +371,68 @@ def fit_latent_preview(latents, images):
   return sol.astype(np.float32)
 
 
+def attention_step_weights(n, attn_maps):
+  """The checked `attn_maps` keyword of the loops: None (no heat maps) or the float32 [n] table
+  of weights by DDIM index -- True: every step counts once; else n finite weights >= 0, not all zero."""
+  if attn_maps is None:
+    return None
+  if isinstance(attn_maps, (bool, np.bool_)):
+    if not attn_maps:
+      raise ValueError("attn_maps must be None, True or a sequence of weights by DDIM index, got False")
+    return np.ones(int(n), dtype=np.float32)
+  if isinstance(attn_maps, (str, bytes)) or np.ndim(attn_maps) != 1:
+    raise ValueError(f"attn_maps must be None, True or {n} weights by DDIM index, got {attn_maps!r}")
+  if any(isinstance(v, (bool, np.bool_)) for v in attn_maps):
+    raise ValueError("attn_maps weights must be numbers, not bools")
+  w = np.asarray(attn_maps, dtype=np.float64)
+  if w.shape != (int(n),):
+    raise ValueError(f"attn_maps must hold one weight per DDIM index ({n}), got {w.shape[0]}")
+  if not np.isfinite(w).all() or (w < 0).any():
+    raise ValueError("attn_maps weights must be finite and >= 0")
+  with np.errstate(over="ignore"):
+    w = w.astype(np.float32)
+  if not np.isfinite(w).all() or not (w > 0).any():
+    raise ValueError("attn_maps weights must be finite in float32 and not all zero")
+  return w
+
+
+def word_heatmaps(heat, spans):
+  """heat [B,Tk,H,W] (last_attention_maps) and spans [(word, [token positions])] (Tokenizer.word_spans) ->
+  [B,n_words,H,W]: the sum of each word's token maps."""
+  heat = np.asarray(heat)
+  if heat.ndim != 4:
+    raise ValueError(f"heat must be [B,Tk,H,W], got {heat.shape}")
+  out = np.zeros((heat.shape[0], len(spans)) + heat.shape[2:], dtype=heat.dtype)
+  for i, (_, pos) in enumerate(spans):
+    pos = [int(p) for p in pos]
+    if any(not 0 <= p < heat.shape[1] for p in pos):
+      raise ValueError(f"token positions {pos} outside the {heat.shape[1]} maps")
+    if pos:
+      out[:, i] = heat[:, pos].sum(axis=1)
+  return out
+
+
+def combine_attention_maps(raw, weight_sum, size=None, resize=None):
+  """The aggregation of last_attention_maps on host arrays: raw = per-layer [B,h_l,w_l,Tk] accumulators ->
+  heat [B,Tk,H,W] = (1 / (weight_sum L)) sum_l resize(raw_l -> (H, W)); `resize(a, (H, W))` maps [B,h,w,Tk] to
+  [B,H,W,Tk] and is needed only when a layer's size differs from `size` (default: the first layer's)."""
+  if not raw:
+    raise ValueError("no layers to combine")
+  if not weight_sum > 0:
+    raise ValueError(f"weight_sum must be positive, got {weight_sum!r}")
+  H, W = (int(v) for v in (size if size is not None else raw[0].shape[1:3]))
+  total = None
+  for a in raw:
+    a = np.asarray(a, dtype=np.float32)
+    if tuple(a.shape[1:3]) != (H, W):
+      if resize is None:
+        raise ValueError(f"a layer of size {a.shape[1:3]} needs `resize` to reach {(H, W)}")
+      a = np.asarray(resize(a, (H, W)), dtype=np.float32)
+    total = a.copy() if total is None else total + a
+  heat = total * np.float32(1.0 / (float(weight_sum) * len(raw)))
+  return np.ascontiguousarray(heat.transpose(0, 3, 1, 2))
+
+
 def preview_slots(num_ddim_steps, freq):
   """R = (N - 1) // q + 1: the slots of a preview strip; slot r holds the step at DDIM index r * q."""
   return (int(num_ddim_steps) - 1) // int(freq) + 1
@@ -640,6 +702,10 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     self._pv_scale = None
     self._pv_mode = "bilinear"
     self._pv_last = None
+    self._am_graph = None                        # the steps captured with heat maps: a slot of
+    self._am_graph_key = None                    # their own too
+    self._am_tab = None                          # the weights by DDIM index on the device (values change in place)
+    self._am_last = None
     self.last_step_ms = None
 
   # ---- the steps' temb projections, once per sampler ---------------------------------
@@ -665,9 +731,9 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
   # wait in _states, so a sampler that alternates between two shapes allocates and captures each
   # once.  What the graphs of every shape read alike (_rng, _gtab, the tables, the device counter) is not listed.
   _SHAPE_BUFFERS = ("_xt", "_x2", "_eps", "_ring", "_start", "_noise_buf", "_q_buf", "_z0_buf", "_mask_buf", "_t_buf",
-                    "_x_win", "_eps_win", "_win_key", "_win_wy", "_win_wx", "_pv_x0", "_pv_a", "_pv_b")
+                    "_x_win", "_eps_win", "_win_key", "_win_wy", "_win_wx", "_pv_x0", "_pv_a", "_pv_b", "_am_accs")
   _SHAPE_GRAPHS = ("_graph", "_graph_key", "_sched_graphs", "_sched_key", "_inv_graph", "_inv_graph_key",
-                   "_pv_graph", "_pv_graph_key", "_pv_sched_graphs", "_pv_sched_key")
+                   "_pv_graph", "_pv_graph_key", "_pv_sched_graphs", "_pv_sched_key", "_am_graph", "_am_graph_key")
 
   def _alloc_state(self, B, h, w, c):
     key = (B, h, w, c)
@@ -685,6 +751,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
         self._state_key = key
         return
       self._graph_key = self._sched_key = self._inv_graph_key = self._pv_graph_key = self._pv_sched_key = None
+      self._am_graph_key = None
       dev, f32 = self.device, torch.float32
       self._xt = torch.empty(B, h, w, c, dtype=f32, device=dev)
       self._x2 = torch.empty(2 * B, h, w, c, dtype=f32, device=dev)
@@ -712,6 +779,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     self._inv_graph = None
     self._pv_graph = None
     self._pv_sched_graphs = {}
+    self._am_graph = None
 
   # ---- latent previews --------------------------------------------------
   def set_preview(self, proj, scale=None, mode="bilinear"):
@@ -809,6 +877,71 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     return dict(sample=np.ascontiguousarray(a.cpu().numpy().swapaxes(0, 1)),
                 pred_x0=np.ascontiguousarray(b.cpu().numpy().swapaxes(0, 1)), indices=indices,
                 written=indices <= k - 1)
+
+  # ---- cross-attention heat maps ------------------------------------------
+  @staticmethod
+  def _no_attn_maps(attn_maps, what):
+    if attn_maps is not None:
+      raise ValueError(f"attn_maps and {what} do not combine")
+
+  def _attn_maps_on(self, attn_maps, attn_layers, gsched, preview_freq, record):
+    """The checked heat-map keywords of a loop call: None, or (weights float32 [N] on the host, the layers as a sorted
+    tuple) with the weights copied into the device table the captured steps read."""
+    if attn_maps is None:
+      if attn_layers is not None:
+        raise ValueError("attn_layers needs attn_maps")
+      return None
+    w = attention_step_weights(len(self._ddim_steps), attn_maps)
+    if gsched is not None:
+      raise ValueError("attn_maps and a guidance schedule (a sequence guidance_scale or guidance_interval) do not combine")
+    self._no_attn_maps(None if preview_freq is None else attn_maps, "preview_freq")
+    self._no_attn_maps(None if record is None else attn_maps, "record=")
+    unet = self._unet
+    if not all(hasattr(unet, a) for a in ("capture_attention", "attention_layers", "reset_attention_maps", "sts")):
+      raise ValueError("attn_maps needs a U-Net with capture_attention")
+    n_st = len(unet.sts)
+    layers = tuple(range(n_st)) if attn_layers is None else tuple(sorted(int(n) for n in attn_layers))
+    if not layers or len(set(layers)) != len(layers) or not all(0 <= n < n_st for n in layers):
+      raise ValueError(f"attn_layers must be distinct indices below {n_st}, got {attn_layers!r}")
+    if self._am_tab is None or self._am_tab.numel() != len(w):
+      self._am_tab = torch.empty(len(w), dtype=torch.float32, device=self.device)
+      self._am_graph = None
+      for saved in self._states.values():
+        saved.update({"_am_graph": None})
+    self._am_tab.copy_(torch.from_numpy(w))
+    return w, layers
+
+  def last_attention_maps(self, size=None, layers=None, mode="bilinear", raw=False):
+    """The heat maps of the last loop run with attn_maps: dict(heat= float32 NumPy [B,Tk,H,W], layers= the transformer
+    blocks summed, weight_sum= the weights of the DDIM indices the loop ran); heat[b, j] = (1 / (weight_sum L)) sum
+    over the L layers of their accumulators [B,h,w,Tk] resized to `size` = (H, W) (default: the latent size) with
+    ops.resize_nhwc in `mode`.  `layers`: a subset of the captured ones.  raw=True adds raw=, the per-layer NumPy
+    accumulators [B,h_l,w_l,Tk].  Synchronises."""
+    if self._am_last is None:
+      raise ValueError("no loop has run with attn_maps")
+    wsum, shape, accs = self._am_last
+    if not wsum > 0:
+      raise ValueError("the last loop with attn_maps ran no DDIM index with a positive weight")
+    have = [n for n, _, _, _ in accs]
+    sel = have if layers is None else [int(n) for n in layers]
+    if not sel or len(set(sel)) != len(sel) or any(n not in have for n in sel):
+      raise ValueError(f"layers must be distinct members of the captured layers {have}, got {layers!r}")
+    H, W = (int(v) for v in (shape if size is None else size))
+    if H < 1 or W < 1:
+      raise ValueError(f"size must be positive, got {size!r}")
+    total, raws = None, []
+    for n, h, w, acc in accs:
+      if n not in sel:
+        continue
+      a = acc if (h, w) == (H, W) else ops.resize_nhwc(acc, (H, W), mode)
+      total = a.clone() if total is None else total + a
+      if raw:
+        raws.append(acc.cpu().numpy())
+    heat = total * (1.0 / (wsum * len(sel)))
+    out = dict(heat=np.ascontiguousarray(heat.permute(0, 3, 1, 2).cpu().numpy()), layers=sorted(sel), weight_sum=wsum)
+    if raw:
+      out["raw"] = raws
+    return out
 
   def _set_loop_start(self, start_index):
     """PLMS / DEIS: the loop's first step is the one at DDIM index `start_index` (it has no history)."""
@@ -1109,13 +1242,18 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     self._loop_events = (t0, t1, num_steps)
 
   def _denoise(self, k, set_start, guidance_scale, gsched, noise_table, masked, rng, record, decode=True,
-               preview_freq=None, on_preview=None):
+               preview_freq=None, on_preview=None, attn_maps=None, attn_layers=None):
     """DDIM indices k-1 .. 0 of the configured solver from the latents `set_start()` leaves in _xt / _x2 (what
     ddim_p_sample_loop, its start_index= form and the img2img loop share); returns the decoded images, or with
     decode=False the latents (_xt itself: the current shape's state).  `preview_freq` = q:
     every step also writes pred_x0 and ends with the one preview launch, captured with it in a graph slot of the
-    previews' own; None leaves the keys, the launches and the graphs as they are without the keyword."""
+    previews' own; None leaves the keys, the launches and the graphs as they are without the keyword.  `attn_maps`
+    (DESIGN.md section 18): the U-Net evaluations also add their cross-attention maps into its accumulators, again
+    in a graph slot of their own."""
+    am = self._attn_maps_on(attn_maps, attn_layers, gsched, preview_freq, record)
     q = self._preview_on(preview_freq, on_preview, len(self._ddim_steps))
+    B = self._xt.shape[0]
+    am_accs = getattr(self, "_am_accs", None) or {}
 
     def reset():
       set_start()
@@ -1124,6 +1262,8 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       if q is not None:                        # (outside the graph: what the warm-up and capture steps wrote goes,
         self._pv_a.zero_()                     # and the slots this loop never reaches read 0)
         self._pv_b.zero_()
+      if am is not None:                       # (outside the graph too: the warm-up and capture steps added theirs)
+        self._unet.reset_attention_maps()
 
     def after_step(s):
       index = k - 1 - s
@@ -1153,12 +1293,27 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       return self._finish(self._xt) if decode else self._xt
     gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, masked, self._noise_source, rng,
             self._step_spacing, self._sampler) + pkey
+    if am is not None:
+      # the conditional half of every evaluation, weighted by the table's entry at the device counter: inside the
+      # U-Net the counter holds the step's DDIM index in every mode (the temb launch has pre-decremented it, or the
+      # update moves it afterwards; the uncounted warm-up step sits on the loop's first index), so the bias is 0
+      self._unet.capture_attention(rows=(B, 2 * B), layers=am[1], step_w=self._am_tab, index_bias=0)
+      try:
+        self._sample_loop(k, reset, step, gkey + (("attn", am[1]),), record, slot="_am_graph")
+        fresh = self._unet.attention_layers()
+      finally:
+        self._unet.capture_attention(None)
+      if fresh:                                # (a replayed graph ran no host code: the accumulators are the ones
+        am_accs[am[1]] = fresh                 # its capture saw)
+        self._am_accs = am_accs
+      self._am_last = (float(am[0][:k].astype(np.float64).sum()), tuple(self._xt.shape[1:3]), am_accs[am[1]])
+      return self._finish(self._xt) if decode else self._xt
     self._sample_loop(k, reset, step, gkey, record, **own)
     return self._finish(self._xt) if decode else self._xt
 
   def ddim_p_sample_loop(self, cond_model_inputs, shape, guidance_scale=5., x_T=None,
                          noises=None, seed=0, first_sample_index=0, record=None, guidance_interval=None,
-                         start_index=None, preview_freq=None, on_preview=None):
+                         start_index=None, preview_freq=None, on_preview=None, attn_maps=None, attn_layers=None):
     """model_runners.py:474-509.  Extra inputs the reference lacks: `x_T` [B,h,w,4]
     (else N(0,1) from `seed`, keyed per global sample index), `noises` [N,B,h,w,4]
     indexed by DDIM index (only read when eta > 0), `record` (list: receives x_t
@@ -1173,7 +1328,12 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     pictures of x_t and of its predicted x_0 into slot index / q of two uint8 strips when its DDIM index is a multiple
     of q, with one extra launch inside the captured step; last_previews() returns the strips, and
     `on_preview(ddim_index, sample_u8, pred_x0_u8)` is called on the host after each such step is enqueued with device
-    views [B,H,W,3] of its slot (nothing synchronises unless the callback reads them).  None: nothing changes."""
+    views [B,H,W,3] of its slot (nothing synchronises unless the callback reads them).  None: nothing changes.
+    `attn_maps`: True, or N finite weights >= 0 by DDIM index -- every U-Net evaluation also adds
+    the head-averaged cross-attention probabilities of the conditional rows, times its step's weight, into one
+    accumulator per transformer block (`attn_layers`: indices into the U-Net's blocks, None = all), one extra launch
+    per block inside the captured step; last_attention_maps() returns the per-token heat maps.  Not with guidance
+    schedules, preview_freq or record=.  None: nothing changes."""
     gsched = self._guidance(guidance_scale, guidance_interval)
     n = len(self._ddim_steps)
     k = n
@@ -1185,10 +1345,11 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
         raise ValueError(f"start_index must be an int in [1, {n}], got {start_index!r}")
     context = self._cond_stage_model(cond_model_inputs)                   # :475
     return self._sample_from(context, shape, k, guidance_scale, gsched, x_T, noises, seed, first_sample_index, record,
-                             preview_freq=preview_freq, on_preview=on_preview)
+                             preview_freq=preview_freq, on_preview=on_preview, attn_maps=attn_maps,
+                             attn_layers=attn_layers)
 
   def _sample_from(self, context, shape, k, guidance_scale, gsched, x_T, noises, seed, first_sample_index, record,
-                   decode=True, preview_freq=None, on_preview=None):
+                   decode=True, preview_freq=None, on_preview=None, attn_maps=None, attn_layers=None):
     """ddim_p_sample_loop from the text context on: DDIM indices k-1 .. 0 from x_T."""
     B, h, w, c = (int(s) for s in shape)
     xt = self._x_T(x_T, seed, first_sample_index, B, h, w, c)
@@ -1200,7 +1361,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     noise_table = None if rng else self._eta_noise_table(noises, seed, first_sample_index, B, h, w, c)
     return self._denoise(k, lambda: self._set_x_T(xt, seed, first_sample_index, B), guidance_scale, gsched,
                          noise_table, False, rng, record, decode=decode, preview_freq=preview_freq,
-                         on_preview=on_preview)
+                         on_preview=on_preview, attn_maps=attn_maps, attn_layers=attn_layers)
 
   def _x_T(self, x_T, seed, first_sample_index, B, h, w, c):
     """The caller's x_T on the device; drawn on the host when omitted; None (noise source "device") = drawn on the
@@ -1240,7 +1401,8 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
   def ddim_p_sample_loop_img2img(self, cond_model_inputs, init_images, guidance_scale=5., strength=0.75,
                                  mask=None, encode_noise=None, q_noises=None, noises=None, seed=0,
                                  first_sample_index=0, record=None, guidance_interval=None, image_size=None,
-                                 fit="stretch", resample="lanczos3", preview_freq=None, on_preview=None):
+                                 fit="stretch", resample="lanczos3", preview_freq=None, on_preview=None,
+                                 attn_maps=None, attn_layers=None):
     """img2img (SDEdit) and masked inpainting on the DDIM loop.
     cond_model_inputs: token ids [uncond x B; cond x B].  init_images [B,H,W,3] (or [H,W,3], tiled) float32
     in [-1, 1].  z0 = get_latents(init_images, encode_noise); k = int(strength * N); the loop starts from
@@ -1256,7 +1418,8 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     source images' size ([B,Hs,Ws] or [Hs,Ws], nonzero = keep), reduced over the same box by latent_mask_fit; a mask
     whose extents are the latent ones is read as a latent mask.  `preview_freq` / `on_preview` as in
     ddim_p_sample_loop (the strips have a slot for every multiple of q below N; the loop writes those it reaches, up
-    to (k-1) // q, and leaves the others 0).  Returns the decoded images; the final latents stay in self._xt."""
+    to (k-1) // q, and leaves the others 0); `attn_maps` / `attn_layers` too (the weights stay indexed by DDIM index;
+    weight_sum covers the k indices run).  Returns the decoded images; the final latents stay in self._xt."""
     size = self._image_size(image_size, fit, resample)
     gsched = self._guidance(guidance_scale, guidance_interval)
     n = len(self._ddim_steps)
@@ -1274,10 +1437,11 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     context = self._cond_stage_model(cond_model_inputs)
     z0 = self.get_latents(imgs, noise=encode_noise, seed=seed, first_sample_index=first_sample_index)
     return self._sdedit(context, z0, k, guidance_scale, gsched, mask, q_noises, noises, seed, first_sample_index,
-                        record, preview_freq=preview_freq, on_preview=on_preview)
+                        record, preview_freq=preview_freq, on_preview=on_preview, attn_maps=attn_maps,
+                        attn_layers=attn_layers)
 
   def _sdedit(self, context, z0, k, guidance_scale, gsched, mask, q_noises, noises, seed, first_sample_index, record,
-              preview_freq=None, on_preview=None):
+              preview_freq=None, on_preview=None, attn_maps=None, attn_layers=None):
     """The img2img loop from the latents z0 [B,h,w,c] on: q_sample to the level of steps[k-1], DDIM indices k-1 .. 0
     (with the blend when `mask` is given), decode."""
     n = len(self._ddim_steps)
@@ -1315,12 +1479,13 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
         ops.q_sample(z0_buf, q_buf[k - 1], t_start, sa, sb, self._xt, x_unet_out=self._x2)
 
     return self._denoise(k, set_start, guidance_scale, gsched, noise_table, masked, rng, record,
-                         preview_freq=preview_freq, on_preview=on_preview)
+                         preview_freq=preview_freq, on_preview=on_preview, attn_maps=attn_maps, attn_layers=attn_layers)
 
   # ---- two-pass high-resolution sampling --------------------------------
   def ddim_p_sample_loop_hires(self, cond_model_inputs, shape, hires_shape, strength=0.5, resize="bilinear",
                                guidance_scale=5., x_T=None, noises=None, q_noises=None, seed=0, first_sample_index=0,
-                               record=None, guidance_interval=None, pixel_filter=None, encode_noise=None):
+                               record=None, guidance_interval=None, pixel_filter=None, encode_noise=None,
+                               attn_maps=None):
     """Two-pass sampling ("hires fix").  Pass 1 is ddim_p_sample_loop at `shape` [B,h,w,c], the
     U-Net's training size, without the decode.  Its latents are resized to `hires_shape` [B,H,W,c] on the device
     (ops.resize_nhwc; `resize` "nearest", "bilinear" or "bicubic").  Pass 2 is the unmasked img2img loop from those
@@ -1337,6 +1502,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     resampled to f times the extents of `hires_shape` (ops.resample_nhwc) and encoded again (get_latents with
     `encode_noise` [B,H,W,c], else drawn from hires_seed(seed)'s ENCODE_STREAM); those latents are pass 2's z0 and
     `resize` is not used.  Needs an autoencoder with its encoder that decodes at both sizes."""
+    self._no_attn_maps(attn_maps, "the hires loop")
     shape, hires_shape = tuple(int(v) for v in shape), tuple(int(v) for v in hires_shape)
     if len(shape) != 4 or len(hires_shape) != 4:
       raise ValueError(f"shape {shape} and hires_shape {hires_shape} must both be [B,h,w,c]")
@@ -1505,7 +1671,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
 
   def ddim_invert_loop(self, cond_model_inputs, init_images=None, latents=None, guidance_scale=1., strength=1.,
                        encode_noise=None, seed=0, first_sample_index=0, record=None, image_size=None,
-                       fit="stretch", resample="lanczos3"):
+                       fit="stretch", resample="lanczos3", attn_maps=None):
     """DDIM inversion: the deterministic, first-order DDIM ODE run upwards from z0, whatever
     sampler= and eta the sampler was built with.  cond_model_inputs: token ids [uncond x B; cond x B].  Exactly one
     of `init_images` ([B,H,W,3] or [H,W,3], tiled; float32 in [-1, 1]; z0 = get_latents(init_images, encode_noise))
@@ -1515,6 +1681,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     (eager, no graph).  Returns the latents on the level of steps[k-1], float32 [B,h,w,c] on the device (a copy;
     they also stay in self._xt): ddim_p_sample_loop(x_T=, start_index=k) maps them back.  `image_size` / `fit` /
     `resample` as in ddim_p_sample_loop_img2img, with `init_images` only."""
+    self._no_attn_maps(attn_maps, "the inversion loop")
     size = self._image_size(image_size, fit, resample)
     if size is not None and init_images is None:
       raise ValueError("image_size resamples init_images: it cannot be given with latents")
@@ -1558,7 +1725,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
   def ddim_p_sample_loop_edit(self, source_inputs, target_inputs, init_images, guidance_scale=5., strength=0.75,
                               invert_guidance_scale=1., encode_noise=None, noises=None, seed=0, first_sample_index=0,
                               record=None, guidance_interval=None, image_size=None, fit="stretch",
-                              resample="lanczos3"):
+                              resample="lanczos3", attn_maps=None):
     """Prompt editing of a real image: z0 = get_latents(init_images); k = int(strength * N)
     inversion steps under the source prompt (`source_inputs`, scale `invert_guidance_scale`); then DDIM indices
     k-1 .. 0 of the configured solver under the target prompt (`target_inputs`, `guidance_scale` /
@@ -1566,6 +1733,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     both scales 1 this reconstructs the image.  `record` receives x after each sampling step.  `image_size` / `fit` /
     `resample` as in ddim_p_sample_loop_img2img.  Returns the decoded images; the final latents
     stay in self._xt."""
+    self._no_attn_maps(attn_maps, "the edit loop")
     self._image_size(image_size, fit, resample)
     if np.shape(source_inputs) != np.shape(target_inputs):
       raise ValueError(f"source_inputs {np.shape(source_inputs)} and target_inputs {np.shape(target_inputs)} must "
@@ -1626,7 +1794,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
 
   def ddim_p_sample_loop_panorama(self, cond_model_inputs, shape, window, stride=None, guidance_scale=5., x_T=None,
                                   noises=None, seed=0, first_sample_index=0, record=None, guidance_interval=None,
-                                  wrap=(False, False), window_weights="uniform", wrap_decode_margin=0):
+                                  wrap=(False, False), window_weights="uniform", wrap_decode_margin=0, attn_maps=None):
     """MultiDiffusion (Bar-Tal et al. 2023) on the loop of ddim_p_sample_loop.  `shape` is the
     canvas [B,H,W,c]; `window` = (h, w) the size the U-Net runs at; `stride` = (sy, sx), default half the window
     (at least 1); one int means both axes.  Windows lie at window_origins() along each axis, the last one clamped to the edge.  Every step
@@ -1639,6 +1807,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     mean), "tent", "gaussian" (window_profile) or a pair of positive arrays (wy [h], wx [w]): the fold is the mean
     weighted by wy[jy] * wx[jx] at each window element.  `wrap_decode_margin`: latent cells of circular padding the
     decoder sees on each side of a wrapped axis (cropped from the images; 0 = the plain decode)."""
+    self._no_attn_maps(attn_maps, "the panorama loop")
     if np.ndim(guidance_scale) > 0 or guidance_interval is not None:
       raise ValueError("the panorama loop takes one float guidance_scale: a sequence guidance_scale or a "
                        "guidance_interval is not supported")
@@ -1690,7 +1859,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
 
   def ddim_p_sample_loop_progressive(self, cond_model_inputs, shape, guidance_scale=5.,
                                      record_freq=5, x_T=None, noises=None, seed=0,
-                                     first_sample_index=0, guidance_interval=None):
+                                     first_sample_index=0, guidance_interval=None, attn_maps=None):
     """Intended semantics of model_runners.py:511-575 (the reference version calls a method
     that does not exist, :535, and returns three values to a caller unpacking two,
     run_ldm_sampler.py:90 -- neither bug is reproduced).  Runs the same loop as
@@ -1699,6 +1868,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     insert_mask overwrites a slot on every such step, :545-553), i.e. of index r*record_freq.
     Returns (images [B,H,W,3], sample_progress [B,R,H,W,3], pred_x0_progress [B,R,H,W,3]),
     all decoded with decode_first_stage.  `guidance_scale` / `guidance_interval` as in ddim_p_sample_loop."""
+    self._no_attn_maps(attn_maps, "the progressive sampler")
     gsched = self._guidance(guidance_scale, guidance_interval)
     B, h, w, c = (int(s) for s in shape)
     context = self._cond_stage_model(cond_model_inputs)

@@ -21,7 +21,7 @@ __all__ = [
     "bmm_nt", "conv3x3_small", "groupnorm", "layernorm", "softmax_rows", "attention",
     "time_embedding", "gemv", "cfg_ddim_update", "cfg_ddim_update_masked", "cfg_plms_update", "q_sample",
     "philox_u32", "normal_fill", "q_sample_rng", "cfg_ddim_update_rng", "cfg_plms_update_rng", "cfg_ms_update",
-    "cfg_ms_update_rng", "cfg_sched_update", "cfg_ddim_invert_update", "window_gather", "window_fold", "window_gather_ex", "window_fold_ex", "wrap_pad", "resize_nhwc", "resample_nhwc", "latent_preview", "post_quant", "vq_nearest", "embedding",
+    "cfg_ms_update_rng", "cfg_sched_update", "cfg_ddim_invert_update", "window_gather", "window_fold", "window_gather_ex", "window_fold_ex", "wrap_pad", "resize_nhwc", "resample_nhwc", "latent_preview", "xattn_map", "xattn_map_supported", "post_quant", "vq_nearest", "embedding",
     "minmax_u8", "cast",
 ]
 
@@ -1202,6 +1202,37 @@ def latent_preview(lat_a, proj, frames_a, freq, index=None, index_bias=0, lat_b=
                                _ptr(frames_a), _ptr(frames_b), _ptr(index), int(index_bias), int(freq), R, B, h, w,
                                c, scale, int(mode), _stream()), "ldm_latent_preview")
   return frames_a
+
+
+def xattn_map_supported(heads, tk, s, sp, dtype):
+  """Whether ldm_xattn_map takes this shape (heads >= 1, 1 <= tk <= 80, s <= sp, sp one of layout.ATTN_SP)."""
+  return bool(lib.ldm_xattn_map_supported(int(heads), int(tk), int(s), int(sp), code(dtype)))
+
+
+def xattn_map(q, k, acc, heads, s, sp, log2_scale, step_w=None, index=None, index_bias=0):
+  """Cross-attention heat maps (include/ldm_hip.h): acc [R,T,Tk] (or [R,h,w,Tk], T = h*w) float32
+  += w * the mean over heads of softmax_j(log2_scale * q_h . k_h) in the exp2 domain, q [R,T,heads*sp] and
+  k [R,Tk,heads*sp] float32 or bf16 with the true head size `s` (the dims from s to sp of every head are not read into
+  the products).  q and k may be row slices such as q[B:] and may have a row pitch above heads*sp; acc is contiguous.
+  w = step_w[index[0] + index_bias] (`step_w` device float32 [N], `index` a device int32 tensor, None = 0), 1 without
+  `step_w`; an index outside the table or a zero weight writes nothing."""
+  assert q.dim() == 3 and k.dim() == 3, (tuple(q.shape), tuple(k.shape))
+  R, T, hs = (int(v) for v in q.shape)
+  Tk = int(k.shape[1])
+  assert hs == heads * sp and tuple(k.shape) == (R, Tk, hs), (tuple(q.shape), tuple(k.shape), heads, sp)
+  assert q.dtype == k.dtype and q.stride(2) == 1 and k.stride(2) == 1, (q.dtype, k.dtype, q.stride(), k.stride())
+  assert acc.dtype == torch.float32 and acc.is_contiguous() and acc.numel() == R * T * Tk and acc.shape[0] == R and \
+      acc.shape[-1] == Tk, (acc.dtype, tuple(acc.shape), (R, T, Tk))
+  n_w = 0
+  if step_w is not None:
+    assert step_w.dtype == torch.float32 and step_w.dim() == 1 and step_w.is_contiguous(), (step_w.dtype, step_w.shape)
+    n_w = int(step_w.numel())
+  if index is not None:
+    assert index.dtype == torch.int32 and index.numel() >= 1
+  check(lib.ldm_xattn_map(_ptr(q), q.stride(1), q.stride(0), _ptr(k), k.stride(1), k.stride(0), _ptr(acc), R,
+                          int(heads), T, Tk, int(s), int(sp), float(log2_scale), code(q.dtype), _ptr(step_w), n_w,
+                          _ptr(index), int(index_bias), _stream()), "ldm_xattn_map")
+  return acc
 
 
 def post_quant(latents, scale_factor, kernel_io, bias, out):

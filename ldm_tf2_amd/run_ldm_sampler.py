@@ -79,6 +79,17 @@ step -- and main() saves the two strips, uint8 [B,R,H,W,3], as `preview_sample.n
 default: fitted on the decoder with a few noise latents, which is rough -- tools/fit_preview.py fits one on a run's
 latents) each need `preview_freq`.  The txt2img and img2img loops take it; `window`, `hires_shape`, `source_prompt` and
 `sample_save_progress` cannot be combined with it.  Without `preview_freq` nothing changes.
+
+Cross-attention heat maps: optional `ldm_sampling` key `attention_maps: true`.  Every U-Net
+evaluation of the loop also adds the head-averaged cross-attention probabilities of the prompt's rows into one
+accumulator per transformer block -- one extra launch per block inside the captured step -- and main() saves the
+per-token maps, float32 [B,Tk,H,W], as `attention_maps.npy` and the prompt's words with their token positions as
+`attention_words.json` beside `--out` (model_runners.word_heatmaps sums a word's maps).  `attention_map_steps:
+[i_lo, i_hi]` (an inclusive range of DDIM indices; default: all) restricts the steps that count,
+`attention_map_size: [H, W]` (default: the latent size) is the size the maps are resized to; both need
+`attention_maps`.  The txt2img and img2img loops take it; `guidance_interval`, a list `guidance_scale`,
+`preview_freq`, `window`, `hires_shape`, `source_prompt` and `sample_save_progress` cannot be combined with it.
+Without `attention_maps` nothing changes.
 """
 from __future__ import annotations
 
@@ -352,6 +363,53 @@ def setup_preview(sampler, config, seed):
   sampler.set_preview(proj, scale=pv["scale"], mode=pv["mode"])
 
 
+ATTENTION_MAP_KEYS = ("attention_map_steps", "attention_map_size")
+
+
+def attention_map_settings(config):
+  """`ldm_sampling.attention_maps` with `attention_map_steps` / `attention_map_size` (the
+  reference's YAML has no such keys), checked: None without `attention_maps`, else dict(weights= the loops' attn_maps
+  value, size= (H, W) or None).  The maps belong to the txt2img and img2img loops with one float guidance scale."""
+  samp = config["ldm_sampling"]
+  on = samp.get("attention_maps")
+  if on is None or on is False:
+    for key in ATTENTION_MAP_KEYS:
+      if samp.get(key) is not None:
+        raise ValueError(f"ldm_sampling.{key} needs ldm_sampling.attention_maps")
+    return None
+  if on is not True:
+    raise ValueError(f"ldm_sampling.attention_maps must be true or false, got {on!r}")
+  for key in ("guidance_interval", "preview_freq", "window", "hires_shape", "source_prompt", "sample_save_progress"):
+    if samp.get(key) is not None and samp.get(key) is not False:
+      raise ValueError(f"ldm_sampling.attention_maps cannot be combined with ldm_sampling.{key}")
+  if np.ndim(samp["guidance_scale"]) > 0:
+    raise ValueError("ldm_sampling.attention_maps cannot be combined with a list ldm_sampling.guidance_scale")
+  is_int = lambda v: isinstance(v, int) and not isinstance(v, bool)
+  n = config["ldm"]["num_ddim_steps"] if "num_ddim_steps" in config.get("ldm", {}) else None
+  weights = True
+  rng = samp.get("attention_map_steps")
+  if rng is not None:
+    if not isinstance(rng, (list, tuple)) or len(rng) != 2 or not all(is_int(v) for v in rng) or not 0 <= rng[0] <= rng[1]:
+      raise ValueError(f"ldm_sampling.attention_map_steps must be [i_lo, i_hi] with 0 <= i_lo <= i_hi, got {rng!r}")
+    if n is None:
+      raise ValueError("ldm_sampling.attention_map_steps needs ldm.num_ddim_steps")
+    if rng[1] >= n:
+      raise ValueError(f"ldm_sampling.attention_map_steps {rng!r} exceeds the {n} DDIM indices")
+    weights = [1.0 if rng[0] <= i <= rng[1] else 0.0 for i in range(n)]
+  size = samp.get("attention_map_size")
+  if size is not None:
+    if not isinstance(size, (list, tuple)) or len(size) != 2 or not all(is_int(v) and v >= 1 for v in size):
+      raise ValueError(f"ldm_sampling.attention_map_size must be [H, W] of positive ints, got {size!r}")
+    size = (size[0], size[1])
+  return dict(weights=weights, size=size)
+
+
+def attention_map_kwargs(config):
+  """The loops' keyword of `ldm_sampling.attention_maps`: nothing when the key is absent."""
+  am = attention_map_settings(config)
+  return {} if am is None else dict(attn_maps=am["weights"])
+
+
 def sampling_call(config, token_ids, seed, source_ids=None):
   """(sampler method name, positional args, kwargs) of the call main() makes for `config`.  `source_ids`: the token
   ids of `ldm_sampling.source_prompt` when the key is there."""
@@ -359,6 +417,7 @@ def sampling_call(config, token_ids, seed, source_ids=None):
   base = (token_ids, samp["latent_shape"], samp["guidance_scale"])
   init_fit_kwargs(config)                        # (ValueError: an unknown init_fit or init_filter, whatever the loop)
   preview = preview_kwargs(config)               # (ValueError: a loop without previews, or a key without preview_freq)
+  preview.update(attention_map_kwargs(config))   # (the heat maps go where the previews go, and refuse the same loops)
   for key in PANORAMA_WRAP_KEYS:
     if samp.get(key) is not None and samp.get("window") is None:
       raise ValueError(f"ldm_sampling.{key} needs ldm_sampling.window")
@@ -473,6 +532,18 @@ def main(argv=None):
       path = os.path.join(os.path.dirname(os.path.abspath(args.out)), name)
       print(f"[INFO] Save latent previews to '{path}'...")
       np.save(path, strips[key])
+  am = attention_map_settings(config)
+  if am is not None:
+    import json
+    from .tokenizer import BertWordPieceTokenizer
+    maps = sampler.last_attention_maps(size=am["size"])
+    spans = BertWordPieceTokenizer(samp["vocab_dir"]).word_spans(samp["text_prompt"],
+                                                                 config["cond_stage_model"]["max_seq_len"])
+    out_dir = os.path.dirname(os.path.abspath(args.out))
+    print(f"[INFO] Save cross-attention maps to '{os.path.join(out_dir, 'attention_maps.npy')}'...")
+    np.save(os.path.join(out_dir, "attention_maps.npy"), maps["heat"])
+    with open(os.path.join(out_dir, "attention_words.json"), "w") as f:
+      json.dump([dict(word=w, positions=pos) for w, pos in spans], f)
 
 
 if __name__ == "__main__":

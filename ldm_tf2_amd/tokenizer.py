@@ -109,6 +109,19 @@ class BertWordPieceTokenizer:
     ids = ids + [self.pad_id] * (max_length - len(ids))
     return np.asarray(ids, dtype=np.int64)
 
+  def word_spans(self, text, max_length=77):
+    """[(word, [token positions])] of `encode(text, max_length)`: the basic tokens (lower-cased words and single
+    punctuation marks) in order, each with the positions of its WordPiece pieces in the id row -- position 0 is
+    [CLS], so the first word starts at 1.  A word whose pieces the truncation cuts, in part or whole, is dropped."""
+    spans, pos, room = [], 1, max(0, max_length - 2)
+    for w in self._basic(text):
+      n = len(self._wordpiece(w))
+      if pos - 1 + n > room:
+        break
+      spans.append((w, list(range(pos, pos + n))))
+      pos += n
+    return spans
+
 
 def get_token_ids(prompt, batch_size, vocab_dir, max_length=77):
   """run_ldm_sampler.py:28-46: int64 [2B, max_length]; rows 0..B-1 = the empty

@@ -183,6 +183,10 @@ class UNet:
     self._phase_upsample = bool(phase_upsample)
     self._shared_prefix = bool(shared_prefix)     # forward(paired_rows=True): the CFG pair's common prefix once (A/B: False)
     self._ctx_sel = None                  # the context rows an evaluation attends to (forward(context_rows=)); None = all
+    self._attn_cap = None                 # capture_attention: rows, layers and weight table of the heat maps; None = off
+    self._attn_acc = {}                   # st index -> (h, w, accumulator) of the evaluations made with capture on
+    self._attn_all = {}                   # every accumulator this model has handed out, by (st index, shape)
+    self._fwd_index = None                # the device step counter of the evaluation in flight (forward(index=))
     self._pend = None
     self._model_channels = model_channels
     self._out_channels = out_channels
@@ -268,6 +272,8 @@ class UNet:
     self.temb_total = off
     self.sts = [b[2] for b in self.in_blocks if b[0] == "res" and b[2] is not None]
     self.sts += [self.mid[1]] + [b[1] for b in self.out_blocks if b[1] is not None]
+    for n, st in enumerate(self.sts):
+      st.index = n
 
   # ---- step-invariant cross-attention K / V ------------------------------------------
   def set_context(self, context):
@@ -281,6 +287,8 @@ class UNet:
       ops.cast(context, c2)
       context = c2
     R, Tk, _ = context.shape
+    if self._attn_cap is not None:
+      self._check_attention(self._attn_cap["layers"], Tk)
     tkp = (Tk + 7) // 8 * 8
     with ops.workspace_scope(self._ws):
       for n, st in enumerate(self.sts):
@@ -292,6 +300,63 @@ class UNet:
         ops.linear(context, st.k2, st.ctx_k, bias=st.ms_kbias)
         ops.bmm_nt(context, st.v2, st.ctx_vt, transposed_out=True, bias=st.ms_vbias)
     self._ctx_rows = R
+
+  # ---- cross-attention heat maps ------------------------------------------
+  def _check_attention(self, layers, Tk):
+    for n in layers:
+      st = self.sts[n]
+      if not ops.xattn_map_supported(st.heads, Tk, st.s, st.sp, self.dtype):
+        raise ValueError(f"capture_attention: layer {n} (heads={st.heads}, head size {st.s} padded to {st.sp}) with "
+                         f"{Tk} context tokens is outside ldm_xattn_map's range (at most 80 tokens)")
+
+  def capture_attention(self, rows=None, layers=None, step_w=None, index_bias=0):
+    """Turns the cross-attention heat maps on or off (off: `rows` None, the default).  On, every forward adds, for
+    each transformer block n in `layers` (indices into self.sts; None = all), the head-averaged cross-attention
+    probabilities of the batch rows `rows` = (r0, r1) into a float32 accumulator [r1-r0, h, w, Tk] of this model
+    (attention_layers; one ldm_xattn_map launch per layer in front of its cross-attention, the block without the
+    ldm_st_block form, which never materialises the queries).  `step_w` (device float32 [N]) weights an evaluation
+    by step_w[index[0] + index_bias] with forward's device `index`, a zero or an index outside the table adding
+    nothing; None: every evaluation counts once.  The accumulators keep their addresses, so a captured graph of the
+    forward stays valid; a graph captured with another setting does not see a change made here."""
+    if rows is None:
+      self._attn_cap = None
+      return
+    r0, r1 = (int(v) for v in rows)
+    if not 0 <= r0 < r1:
+      raise ValueError(f"capture_attention: rows must be (r0, r1) with 0 <= r0 < r1, got {rows!r}")
+    layers = list(range(len(self.sts))) if layers is None else [int(n) for n in layers]
+    if not layers or sorted(set(layers)) != sorted(layers) or not all(0 <= n < len(self.sts) for n in layers):
+      raise ValueError(f"capture_attention: layers must be distinct indices below {len(self.sts)}, got {layers!r}")
+    if step_w is not None and (step_w.dtype != torch.float32 or step_w.dim() != 1 or not step_w.is_cuda):
+      raise ValueError("capture_attention: step_w must be a device float32 vector")
+    self._check_attention(layers, 1 if self.sts[0].ctx_k is None else self.sts[0].ctx_k.shape[1])
+    self._attn_cap = dict(rows=(r0, r1), layers=frozenset(layers), step_w=step_w, index_bias=int(index_bias))
+    self._attn_acc = {}                   # (attention_layers lists what THIS setting's evaluations reach)
+
+  def attention_layers(self):
+    """[(st index, h, w, acc)]: the accumulators float32 [r1-r0, h, w, Tk] (device) of the captured layers that an
+    evaluation has reached, in layer order."""
+    if self._attn_cap is None:
+      return []
+    return [(n,) + self._attn_acc[n] for n in sorted(self._attn_cap["layers"]) if n in self._attn_acc]
+
+  def reset_attention_maps(self):
+    """Zeroes every accumulator of this model (all layers and shapes; their addresses stay)."""
+    for acc in self._attn_all.values():
+      acc.zero_()
+
+  def _attn_map(self, st, cap, q, ctx_k, h, w, scale, ms):
+    r0, r1 = cap["rows"]
+    if r1 > q.shape[0]:
+      raise ValueError(f"capture_attention: rows {cap['rows']} exceed the evaluation's {q.shape[0]} rows")
+    Tk = ctx_k.shape[1]
+    acc = self.buf.get(f"xmap{st.index}", (r1 - r0, h, w, Tk), torch.float32, zero=True)
+    self._attn_acc[st.index] = (h, w, acc)
+    self._attn_all[st.index, tuple(acc.shape)] = acc
+    # (matrix-softmax blocks: the folded query projection carries s^-1/2 log2(e) already)
+    ops.xattn_map(q[r0:r1], ctx_k[r0:r1], acc, st.heads, st.s, st.sp, 1.0 if ms else scale * L.MS_LOG2E,
+                  step_w=cap["step_w"], index=self._fwd_index if cap["step_w"] is not None else None,
+                  index_bias=cap["index_bias"])
 
   # ---- blocks ------------------------------------------------------------------------------
   # ---- split-K products whose reduce is fused into the GroupNorm that consumes them ---------------
@@ -410,6 +475,8 @@ class UNet:
     blk = (self._fused_block and fold is not None and st.ffn_aux is not None and self._fused_ffn and self._fused_tail
            and self._fused_xattn and ms and hs == 384 and T % 128 == 0 and ctx_k.shape[1] <= 80 and ctx_vt.shape[2] >= 80
            and Ro * T >= min(self._ffn_min_rows, self._block_min_rows))
+    cap = self._attn_cap if self._attn_cap is not None and st.index in self._attn_cap["layers"] else None
+    blk = blk and cap is None             # (ldm_st_block never materialises the queries the heat maps read)
     if pair and not blk:
       # per-layer path: the pair leaves its common prefix here -- both halves get their copy of the self-attention's
       # output, the residual stream and the block input, and everything below covers all rows
@@ -433,6 +500,8 @@ class UNet:
       if not fuse_ln:
         ops.layernorm(hb, st.ln[1][0], st.ln[1][1], ln, LN_EPS)
       ops.linear(ln, st.q2, q)
+    if cap is not None:
+      self._attn_map(st, cap, q, ctx_k, h, w, scale, ms)
     if xtail:
       # ... with the cross-attention itself in front of it, in place in the LDS panel
       ops.st_xtail(q, ctx_k, ctx_vt, st.o2[0], st.o2[1], hb, fold["geglu"][0], st.ffn_aux, st.ff_out[0],
@@ -501,6 +570,8 @@ class UNet:
       lo, hi = (int(v) for v in context_rows)
       assert 0 <= lo and hi <= self._ctx_rows and hi - lo == R, (context_rows, self._ctx_rows, R)
       assert not paired_rows, "paired_rows needs the whole context"
+      if self._attn_cap is not None:
+        raise ValueError("capture_attention and forward(context_rows=) do not combine")
     if out is None:
       out = torch.empty(R, h, w, self._out_channels, dtype=torch.float32, device=self.device)
     if temb_table is not None:
@@ -511,6 +582,7 @@ class UNet:
       assert not pre_decrement
       tall = self._temb(R, t_rows, steps, index, shared_t)
     self._ctx_sel = None if context_rows is None else slice(lo, lo + R)
+    self._fwd_index = index
     # a CFG pair: the launches in front of the first cross-attention once, on the first R/2 rows
     pair = bool(paired_rows and self._shared_prefix and R % 2 == 0
                 and self.in_blocks[0][0] == "res" and self.in_blocks[0][2] is not None)
