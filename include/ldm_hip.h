@@ -714,6 +714,44 @@ int ldm_xattn_map(const void* q, int64_t ldq, int64_t q_bs, const void* k, int64
                   int heads, int T, int Tk, int S, int sp, float log2_scale, int dtype, const float* step_w, int n_w,
                   const int32_t* index, int index_bias, void* stream);
 
+/*
+ * DiffEdit.
+ *
+ * ldm_eps_contrast_accum: the contrast of the two halves of a paired U-Net output, ADDED into acc.
+ *   eps_all [2B][cells][c] float32: rows 0 .. B-1 the source prompt's eps (e_src), rows B .. 2B-1 the target's (e_tgt);
+ *   acc [B][cells] float32, read-modify-write.
+ * Per cell, with d_j = e_tgt[j] - e_src[j]:  s = |d_0|;  s = s + |d_j| for j = 1 .. c-1 ascending;  acc = acc + s.
+ * Plain float32 operations in exactly that order -- no multiply, so nothing can contract -- and a NumPy float32
+ * restatement is bit-identical.  A NaN in one channel reaches its own cell only.  `counter` (may be NULL): *counter is
+ * decremented by a one-thread launch after this one, so every block has read what it needed first; the next
+ * ldm_q_sample reads its noise row through it.  c == 4: four cells per thread, 16-byte loads of both halves and one
+ * 16-byte acc load and store; the cells % 4 tail and any other c in 1..16 take a scalar path.  Grid-stride.
+ * LDM_ERR_ARG, nothing launched: a null eps_all or acc; B or cells below 1; c outside 1..16; eps_all or acc not
+ * 16-byte aligned at c == 4 (4-byte at any other c).
+ *
+ * ldm_contrast_mask: acc [B][h][w] float32 -> mask_out [B][h][w] float32, 1 = keep.  Per sample b:
+ *   mean_b = (sum_p acc[b][p]) / (h w);  thr_b = tau * mean_b;  edit[p] = acc[b][p] > thr_b, written exactly so (a NaN
+ *   in the cell or in the sum keeps the cell; an all-zero sample edits nothing; no division by the mean);
+ *   edit'[y][x] = OR of edit over the (2 dilate + 1)^2 neighbourhood clipped to the image;  mask = 1 - edit'.
+ * mean_out, thr_out float32 [B] and count_out int32 [B] (the edited cells after dilation) may each be NULL.  The sum is
+ * 256 strided float32 partial sums folded by a fixed tree: within h w 2^-24 relative of the exact sum for non-negative
+ * terms, and the same bits on every run (no atomics).  One 256-thread workgroup per sample keeps the sample's
+ * thresholded bytes in LDS, hence ldm_contrast_mask_supported: h, w >= 1, h w <= 65536, dilate in 0..3.
+ * LDM_ERR_ARG, nothing launched: a null acc or mask_out, B below 1, a shape outside _supported.
+ *
+ * ldm_store_row: table[row][0 .. n) = src[0 .. n) for row = index_sign * (*index) + index_bias; a row outside [0, rows)
+ * writes nothing at all.  The inverse of ldm_select_row: it keeps a step's output in the row a device-resident counter
+ * selects, inside a captured step.  *index is only read.  16-byte copies: n % 4 == 0, row_stride % 4 == 0 and >= n, src
+ * and table 16-byte aligned, index_sign 1 or -1; else LDM_ERR_ARG.
+ */
+int ldm_eps_contrast_accum(const float* eps_all, float* acc, int32_t* counter, int B, int64_t cells, int c,
+                           void* stream);
+int ldm_contrast_mask_supported(int h, int w, int dilate);
+int ldm_contrast_mask(const float* acc, float* mask_out, float* mean_out, float* thr_out, int32_t* count_out, int B,
+                      int h, int w, float tau, int dilate, void* stream);
+int ldm_store_row(const float* src, float* table, int64_t row_stride, int rows, const int32_t* index, int index_sign,
+                  int index_bias, int64_t n, void* stream);
+
 /* decode_first_stage prologue (model_runners.py:426 + autoencoder.py:362,434):
  * out = Dense_{C->C}(latents / scale_factor), C <= 8; float32 in, out_dtype out. */
 int ldm_post_quant(const float* latents, float scale_factor, const float* kernel_io,

@@ -65,6 +65,13 @@ RGB pictures of x_t and of the predicted x_0 every q DDIM indices: the step's up
 ldm_latent_preview launch inside the captured step maps both through the matrix of set_preview / fit_preview, enlarges
 and quantises them into the slot the device-resident index selects.  Those steps are captured in graph slots of their
 own; without the keyword every key, launch and graph is the one it was.
+
+ddim_p_sample_loop_diffedit keeps the prompt edit inside a mask: diffedit_mask replays one
+captured contrast step per noise draw (ldm_q_sample by table row, the paired U-Net call against the two prompts'
+conditional contexts, ldm_eps_contrast_accum) and thresholds the map on the device (ldm_contrast_mask);
+ddim_invert_loop(trajectory=True) stores every inversion level with one ldm_store_row launch inside its captured step;
+the sampling loop's masked blend then reads that trajectory where the img2img loop reads q_sample(z0, Q).  Three graph
+slots of their own; without the keywords every key, launch and graph is the one it was.
 """
 from __future__ import annotations
 
@@ -110,6 +117,7 @@ def normal_latents(seed, first_index, count, shape_hwc, stream=None):
 ENCODE_STREAM = 1 << 30          # posterior noise E of get_latents
 Q_STREAM = (1 << 30) + 1         # + i: forward-diffusion noise Q[i] of DDIM index i
 PREVIEW_FIT_STREAM = 1 << 31     # the stand-in latents of fit_preview (above Q_STREAM + i for every i < 2^30)
+MAP_STREAM = 3 << 29             # + r: draw r of DiffEdit's contrast map (above Q_STREAM + i for i < 2^29 - 1, below 2^31)
 # noise_source="device" only (the host draws key x_T and the eta noise by the seed word, see normal_latents): the
 # stream word is the third counter word of the device generator; the four ranges are disjoint for i < 2^29.
 XT_STREAM = 0                    # x_T
@@ -706,6 +714,19 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     self._am_graph_key = None                    # their own too
     self._am_tab = None                          # the weights by DDIM index on the device (values change in place)
     self._am_last = None
+    # DiffEdit: the contrast step, the inversion that keeps its trajectory and the sampling
+    # whose blend reads it are captured in slots of their own, beside every graph above
+    self._dm_graph = None
+    self._dm_graph_key = None
+    self._invt_graph = None
+    self._invt_graph_key = None
+    self._de_graph = None
+    self._de_graph_key = None
+    self._dm_counters = None                     # two device ints: the contrast step's DDIM index, its draw counter
+    self._de_qcoef = None                        # the blend's constant coefficients (0, 1): q_sample(z0, Q) = Q
+    self._blend_traj = False                     # whether _blend_kwargs hands the blend the trajectory for Q
+    self._dm_last = None
+    self._traj_last = None
     self.last_step_ms = None
 
   # ---- the steps' temb projections, once per sampler ---------------------------------
@@ -731,9 +752,11 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
   # wait in _states, so a sampler that alternates between two shapes allocates and captures each
   # once.  What the graphs of every shape read alike (_rng, _gtab, the tables, the device counter) is not listed.
   _SHAPE_BUFFERS = ("_xt", "_x2", "_eps", "_ring", "_start", "_noise_buf", "_q_buf", "_z0_buf", "_mask_buf", "_t_buf",
-                    "_x_win", "_eps_win", "_win_key", "_win_wy", "_win_wx", "_pv_x0", "_pv_a", "_pv_b", "_am_accs")
+                    "_x_win", "_eps_win", "_win_key", "_win_wy", "_win_wx", "_pv_x0", "_pv_a", "_pv_b", "_am_accs",
+                    "_traj", "_dm_acc", "_dm_out", "_dm_noise", "_dm_t")
   _SHAPE_GRAPHS = ("_graph", "_graph_key", "_sched_graphs", "_sched_key", "_inv_graph", "_inv_graph_key",
-                   "_pv_graph", "_pv_graph_key", "_pv_sched_graphs", "_pv_sched_key", "_am_graph", "_am_graph_key")
+                   "_pv_graph", "_pv_graph_key", "_pv_sched_graphs", "_pv_sched_key", "_am_graph", "_am_graph_key",
+                   "_dm_graph", "_dm_graph_key", "_invt_graph", "_invt_graph_key", "_de_graph", "_de_graph_key")
 
   def _alloc_state(self, B, h, w, c):
     key = (B, h, w, c)
@@ -751,7 +774,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
         self._state_key = key
         return
       self._graph_key = self._sched_key = self._inv_graph_key = self._pv_graph_key = self._pv_sched_key = None
-      self._am_graph_key = None
+      self._am_graph_key = self._dm_graph_key = self._invt_graph_key = self._de_graph_key = None
       dev, f32 = self.device, torch.float32
       self._xt = torch.empty(B, h, w, c, dtype=f32, device=dev)
       self._x2 = torch.empty(2 * B, h, w, c, dtype=f32, device=dev)
@@ -780,6 +803,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     self._pv_graph = None
     self._pv_sched_graphs = {}
     self._am_graph = None
+    self._dm_graph = self._invt_graph = self._de_graph = None
 
   # ---- latent previews --------------------------------------------------
   def set_preview(self, proj, scale=None, mode="bilinear"):
@@ -1007,6 +1031,12 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     """The inpainting blend's arguments of an update: none unless `masked`; the Q table unless Q is drawn (`rng`)."""
     if not masked:
       return {}
+    if self._blend_traj:
+      # DiffEdit (DESIGN.md section 19): Q = the inversion trajectory under the coefficients (0, 1), so the blend's
+      # q_sample(z0, Q[j]) is traj[j] bit for bit; always the table-reading entries
+      assert not rng
+      return dict(z0=self._z0_buf, mask=self._mask_buf, q_coef=self._de_qcoef, q_noise=self._traj,
+                  q_index_stride=self._traj[0].numel())
     blend = dict(z0=self._z0_buf, mask=self._mask_buf, q_coef=self._device_q_tables()[2])
     if not rng:
       blend.update(q_noise=self._q_buf, q_index_stride=self._q_buf[0].numel())
@@ -1272,6 +1302,11 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
 
     # previews: the update also writes pred_x0, one launch follows it, the key says so and the graphs have their slots
     pv, pkey, own, own_sched = {}, (), {}, {}
+    if self._blend_traj:
+      # the blend reads the trajectory: the key says so and the step has a slot of its own, so
+      # this loop and the masked img2img loop never share a captured step
+      assert masked and not rng and gsched is None and q is None and am is None
+      pkey, own = (("traj_blend",),), dict(slot="_de_graph")
     if q is not None:
       pv, pkey = dict(pred_x0_out=self._pv_x0), (("preview", q, self._pv_scale, self._pv_mode),)
       own, own_sched = dict(slot="_pv_graph", after_step=after_step), dict(slot="_pv_sched", after_step=after_step)
@@ -1671,7 +1706,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
 
   def ddim_invert_loop(self, cond_model_inputs, init_images=None, latents=None, guidance_scale=1., strength=1.,
                        encode_noise=None, seed=0, first_sample_index=0, record=None, image_size=None,
-                       fit="stretch", resample="lanczos3", attn_maps=None):
+                       fit="stretch", resample="lanczos3", attn_maps=None, trajectory=False):
     """DDIM inversion: the deterministic, first-order DDIM ODE run upwards from z0, whatever
     sampler= and eta the sampler was built with.  cond_model_inputs: token ids [uncond x B; cond x B].  Exactly one
     of `init_images` ([B,H,W,3] or [H,W,3], tiled; float32 in [-1, 1]; z0 = get_latents(init_images, encode_noise))
@@ -1680,7 +1715,11 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     sqrt(1 - a_prev[i]) e) / sqrt(a_prev[i]), x <- (x0 + c2[i] e) / c1[i].  `record` receives x after each step
     (eager, no graph).  Returns the latents on the level of steps[k-1], float32 [B,h,w,c] on the device (a copy;
     they also stay in self._xt): ddim_p_sample_loop(x_T=, start_index=k) maps them back.  `image_size` / `fit` /
-    `resample` as in ddim_p_sample_loop_img2img, with `init_images` only."""
+    `resample` as in ddim_p_sample_loop_img2img, with `init_images` only.
+    `trajectory=True`: every step also stores its output, the latents on the level of steps[j]
+    for the inversion index j, into row j of a table [N,B,h,w,c] the sampler owns -- one ldm_store_row launch after
+    the update, inside the captured step, in a graph slot of its own; last_trajectory() returns the k rows.  False:
+    the launches, the graph and its key are what they were."""
     self._no_attn_maps(attn_maps, "the inversion loop")
     size = self._image_size(image_size, fit, resample)
     if size is not None and init_images is None:
@@ -1719,8 +1758,32 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     # (the scale is an argument of the captured launch, and the conditional-only form has none; the depth k is not
     # in the key: the counter is on the device)
     gkey = ("invert", None if cond_only else guidance_scale, self._ctx_shape, self._step_spacing)
+    if trajectory:
+      n = len(self._ddim_steps)
+      if getattr(self, "_traj", None) is None:
+        self._traj = torch.zeros(n, B, h, w, c, dtype=torch.float32, device=self.device)
+        self._invt_graph = self._de_graph = None
+
+      def step(dec):
+        # after the update the counter holds N-1-j when the U-Net's first launch pre-decremented it and one less when
+        # the update itself moved it (temb_table=False); the uncounted warm-up step moves nothing
+        self._step_invert(guidance_scale, dec)
+        ops.store_row(self._xt, self._traj, self._index_dev, index_sign=-1,
+                      index_bias=n - 1 - (1 if dec and not self._pre_dec else 0))
+
+      self._sample_loop(k, reset, step, gkey + ("trajectory",), record, slot="_invt_graph")
+      self._traj_last = (k, self._traj)
+      return self._xt.clone()
     self._sample_loop(k, reset, lambda dec: self._step_invert(guidance_scale, dec), gkey, record, slot="_inv_graph")
     return self._xt.clone()
+
+  def last_trajectory(self):
+    """The trajectory of the last ddim_invert_loop(trajectory=True): float32 [k,B,h,w,c] on the device, row j the
+    latents on the level of steps[j] (a copy of the table's first k rows)."""
+    if self._traj_last is None:
+      raise ValueError("no inversion has run with trajectory=True")
+    k, traj = self._traj_last
+    return traj[:k].clone()
 
   def ddim_p_sample_loop_edit(self, source_inputs, target_inputs, init_images, guidance_scale=5., strength=0.75,
                               invert_guidance_scale=1., encode_noise=None, noises=None, seed=0, first_sample_index=0,
@@ -1746,6 +1809,200 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     return self.ddim_p_sample_loop(target_inputs, tuple(x.shape), guidance_scale, x_T=x, noises=noises, seed=seed,
                                    first_sample_index=first_sample_index, record=record,
                                    guidance_interval=guidance_interval, start_index=k)
+
+  # ---- DiffEdit -----------------------------------------------------------
+  def _diffedit_args(self, source_inputs, target_inputs, mask_strength, num_maps, mask_threshold, mask_clamp_ratio,
+                     mask_dilate):
+    """The checked mask keywords -> (k_m, n, tau, dilate); raises before anything is allocated."""
+    if np.shape(source_inputs) != np.shape(target_inputs):
+      raise ValueError(f"source_inputs {np.shape(source_inputs)} and target_inputs {np.shape(target_inputs)} must "
+                       "have the same shape")
+    if isinstance(num_maps, bool) or int(num_maps) != num_maps or int(num_maps) < 1:
+      raise ValueError(f"num_maps must be an int of at least 1, got {num_maps!r}")
+    if isinstance(mask_dilate, bool) or int(mask_dilate) != mask_dilate or not 0 <= int(mask_dilate) <= 3:
+      raise ValueError(f"mask_dilate must be an int in [0, 3], got {mask_dilate!r}")
+    try:
+      k_m = img2img_start(mask_strength, len(self._ddim_steps))
+    except ValueError as e:
+      raise ValueError(f"mask_strength: {e}") from None
+    tau = float(mask_threshold) * float(mask_clamp_ratio)
+    if not np.isfinite(tau) or tau < 0.:
+      raise ValueError(f"mask_threshold * mask_clamp_ratio must be finite and not negative, got {mask_threshold!r} * "
+                       f"{mask_clamp_ratio!r}")
+    return k_m, int(num_maps), tau, int(mask_dilate)
+
+  def _edit_z0(self, init_images, latents, B, size, fit, resample, encode_noise, seed, first_sample_index):
+    """z0 [B,h,w,c] float32 of exactly one of `init_images` (get_latents, after image_size=) and `latents`."""
+    if (init_images is None) == (latents is None):
+      raise ValueError("exactly one of init_images and latents must be given")
+    if latents is None:
+      imgs = self._init_images(init_images, B)
+      if size is not None:
+        imgs = self._fit_images(imgs, size, fit, resample)
+      return self.get_latents(imgs, noise=encode_noise, seed=seed, first_sample_index=first_sample_index)
+    if size is not None:
+      raise ValueError("image_size resamples init_images: it cannot be given with latents")
+    z0 = torch.as_tensor(np.asarray(latents) if not isinstance(latents, torch.Tensor) else latents, dtype=torch.float32)
+    if z0.dim() != 4 or z0.shape[0] != B:
+      raise ValueError(f"latents must be [B={B},h,w,c], got {tuple(z0.shape)}")
+    return z0
+
+  def diffedit_mask(self, source_inputs, target_inputs, init_images=None, latents=None, mask_strength=0.5, num_maps=10,
+                    mask_threshold=0.5, mask_clamp_ratio=3., mask_dilate=0, map_noises=None, encode_noise=None, seed=0,
+                    first_sample_index=0, image_size=None, fit="stretch", resample="lanczos3"):
+    """DiffEdit's mask (Couairon et al. 2022): where the source and the target prompt disagree
+    about the noise in an image.  Both id arrays are [uncond x B; cond x B]; exactly one of `init_images` and `latents`
+    gives z0.  k_m = int(mask_strength * N), t_m = steps[k_m - 1]; for each of n = `num_maps` draws r (in this order)
+    x_r = q_sample(z0, t_m, M[r]), one paired U-Net evaluation of [x_r; x_r] against [source cond x B; target cond x B]
+    and acc[b,p] += sum_j |e_tgt - e_src| (ldm_eps_contrast_accum): one captured step replayed n times.  M is
+    `map_noises` [n,B,h,w,c], else drawn per global sample index from the streams MAP_STREAM + r (by ldm_normal_fill
+    when the noise source is "device").  Then ldm_contrast_mask: edit = acc > tau * (the sample's mean of acc), tau =
+    mask_threshold * mask_clamp_ratio (HF diffusers' clamp(map, 0, ratio mean) / (ratio mean) > threshold with the
+    mean per sample), dilated by `mask_dilate` cells (0..3).  Returns the mask float32 [B,h,w] on the device, 1 = keep
+    (a copy); last_contrast_map() has the map and the statistics.  `image_size` / `fit` / `resample` as in
+    ddim_p_sample_loop_img2img, with `init_images` only."""
+    size = self._image_size(image_size, fit, resample)
+    k_m, n, tau, dilate = self._diffedit_args(source_inputs, target_inputs, mask_strength, num_maps, mask_threshold,
+                                              mask_clamp_ratio, mask_dilate)
+    B = len(source_inputs) // 2
+    z0 = self._edit_z0(init_images, latents, B, size, fit, resample, encode_noise, seed, first_sample_index)
+    return self._diffedit_mask(source_inputs, target_inputs, z0, k_m, n, tau, dilate, map_noises, seed,
+                               first_sample_index).clone()
+
+  def _diffedit_mask(self, source_inputs, target_inputs, z0, k_m, n, tau, dilate, map_noises, seed, first_sample_index):
+    """diffedit_mask from z0 on; returns the sampler's own mask buffer."""
+    B, h, w, c = (int(v) for v in z0.shape)
+    if not ops.contrast_mask_supported(h, w, dilate):
+      raise ValueError(f"the mask kernel takes latents of at most 65536 cells, got {h} x {w}")
+    ids = np.concatenate([np.asarray(source_inputs)[B:], np.asarray(target_inputs)[B:]], axis=0)
+    context = self._cond_stage_model(ids)
+    self._alloc_state(B, h, w, c)
+    self._set_context(context)
+    z0_buf = self._owned("_z0_buf", z0, (B, h, w, c))
+    # the draw table is stored reversed, as the inversion's tables are: the draw counter only walks down (from n - 1),
+    # and row n-1-r holds draw r, so the draws run r = 0 .. n-1
+    if map_noises is None and self._noise_source == "device":
+      buf = getattr(self, "_dm_noise", None)
+      if buf is None or tuple(buf.shape) != (n, B, h, w, c):
+        buf = self._dm_noise = torch.zeros(n, B, h, w, c, dtype=torch.float32, device=self.device)
+        self._drop_graphs()
+      rng = self._set_rng(seed, first_sample_index)
+      for r in range(n):
+        ops.normal_fill(buf[n - 1 - r], rng, MAP_STREAM + r)
+    else:
+      if map_noises is None:
+        map_noises = np.stack([normal_latents(seed, first_sample_index, B, (h, w, c), stream=MAP_STREAM + r)
+                               for r in range(n)])
+      m = torch.as_tensor(np.asarray(map_noises) if not isinstance(map_noises, torch.Tensor) else map_noises,
+                          dtype=torch.float32)
+      if tuple(m.shape) != (n, B, h, w, c):
+        raise ValueError(f"map_noises: shape {tuple(m.shape)}, expected {(n, B, h, w, c)}")
+      buf = self._owned("_dm_noise", m.flip(0), (n, B, h, w, c))
+    t_m = self._owned("_dm_t", np.full(B, self._ddim_steps[k_m - 1]), (B,), dtype=torch.int32)
+    if getattr(self, "_dm_acc", None) is None:
+      self._dm_acc = torch.zeros(B, h, w, dtype=torch.float32, device=self.device)
+      self._dm_out = (torch.empty(B, h, w, dtype=torch.float32, device=self.device),
+                      torch.empty(B, dtype=torch.float32, device=self.device),
+                      torch.empty(B, dtype=torch.float32, device=self.device),
+                      torch.empty(B, dtype=torch.int32, device=self.device))
+      self._dm_graph = None
+    if self._dm_counters is None:
+      self._dm_counters = torch.zeros(2, dtype=torch.int32, device=self.device)
+    t_index, draw = self._dm_counters[0:1], self._dm_counters[1:2]
+    sa, sb, _ = self._device_q_tables()
+    acc, stride = self._dm_acc, buf[0].numel()
+
+    def reset():
+      t_index.fill_(k_m - 1)                   # (the U-Net's time index: read, never moved)
+      draw.fill_(n - 1)
+      acc.zero_()                              # (outside the graph: the warm-up and capture steps added theirs)
+
+    def step(dec):
+      ops.q_sample(z0_buf, buf, t_m, sa, sb, self._xt, x_unet_out=self._x2, index=draw, noise_index_stride=stride)
+      kw = dict(self._temb_kwargs(False))
+      self._unet.forward(self._x2, steps=self._steps_dev, index=t_index, out=self._eps, paired_rows=True, **kw)
+      ops.eps_contrast_accum(self._eps, acc, counter=draw if dec else None)
+
+    gkey = ("diffedit_map", self._ctx_shape, self._step_spacing)
+    self._sample_loop(n, reset, step, gkey, None, slot="_dm_graph")
+    mask, mean, thr, count = self._dm_out
+    ops.contrast_mask(acc, mask, tau, dilate, mean_out=mean, thr_out=thr, count_out=count)
+    self._dm_last = (n, c, acc, self._dm_out)
+    return mask
+
+  def last_contrast_map(self):
+    """Of the last mask estimate: dict(map= float32 [B,h,w], acc / (c n): the mean absolute difference of the two
+    prompts' eps per cell; mask= float32 [B,h,w], 1 = keep; mean=, threshold= float32 [B] in acc's units (the scale
+    1 / (c n) cancels in the rule); edited= int32 [B], the edited cells after dilation), all NumPy.  Synchronises."""
+    if self._dm_last is None:
+      raise ValueError("no contrast map has been estimated")
+    n, c, acc, (mask, mean, thr, count) = self._dm_last
+    return dict(map=(acc / float(c * n)).cpu().numpy(), mask=mask.cpu().numpy(), mean=mean.cpu().numpy(),
+                threshold=thr.cpu().numpy(), edited=count.cpu().numpy())
+
+  def ddim_p_sample_loop_diffedit(self, source_inputs, target_inputs, init_images, guidance_scale=5., strength=0.75,
+                                  invert_guidance_scale=1., mask=None, mask_strength=0.5, num_maps=10,
+                                  mask_threshold=0.5, mask_clamp_ratio=3., mask_dilate=0, map_noises=None,
+                                  encode_noise=None, noises=None, record=None, seed=0, first_sample_index=0,
+                                  image_size=None, fit="stretch", resample="lanczos3", guidance_interval=None,
+                                  preview_freq=None, on_preview=None, attn_maps=None, attn_layers=None):
+    """DiffEdit: the prompt edit of ddim_p_sample_loop_edit kept inside a mask.  z0 =
+    get_latents(init_images), once; the mask is diffedit_mask's estimate on z0 (its keywords above) unless `mask`
+    (latent [B,h,w] or [h,w], 1 = keep) is given; k = int(strength * N) inversion steps under the source prompt keep
+    their trajectory traj[0 .. k-1]; sampling starts from traj[k-1] under the target prompt with the configured solver,
+    and before the step at every index i < k-1, x <- m traj[i] + (1 - m) x -- the update launch's own blend reading
+    the trajectory for Q under the coefficients (0, 1), so a kept cell is traj[i] bit for bit; nothing is blended at
+    index 0.  Every solver, step table and noise source; the eta noise comes from `noises` or the loop's table.
+    `record` receives x after each sampling step (eager, no graph).  A guidance schedule or interval, previews and
+    attn_maps do not combine with it.  Returns the decoded images; the final latents stay in self._xt."""
+    if np.ndim(guidance_scale) > 0 or guidance_interval is not None:
+      raise ValueError("the DiffEdit loop takes one float guidance_scale: a guidance schedule (a sequence "
+                       "guidance_scale or guidance_interval) is not supported")
+    if preview_freq is not None or on_preview is not None:
+      raise ValueError("preview_freq and the DiffEdit loop do not combine")
+    if attn_layers is not None and attn_maps is None:
+      raise ValueError("attn_layers needs attn_maps")
+    self._no_attn_maps(attn_maps, "the DiffEdit loop")
+    size = self._image_size(image_size, fit, resample)
+    k_m, n_maps, tau, dilate = self._diffedit_args(source_inputs, target_inputs, mask_strength, num_maps,
+                                                   mask_threshold, mask_clamp_ratio, mask_dilate)
+    n = len(self._ddim_steps)
+    k = img2img_start(strength, n)
+    B = len(source_inputs) // 2
+    z0 = self._edit_z0(init_images, None, B, size, fit, resample, encode_noise, seed, first_sample_index)
+    _, h, w, c = z0.shape
+    if mask is None:
+      mask = self._diffedit_mask(source_inputs, target_inputs, z0, k_m, n_maps, tau, dilate, map_noises, seed,
+                                 first_sample_index)
+    else:
+      mask = torch.as_tensor(np.asarray(mask) if not isinstance(mask, torch.Tensor) else mask, dtype=torch.float32)
+      if mask.dim() == 2:
+        mask = mask[None].expand(B, *mask.shape)
+      if tuple(mask.shape) != (B, h, w):
+        raise ValueError(f"mask must be [B,h,w] = {(B, h, w)} (or [h,w]) at latent resolution, "
+                         f"got {tuple(mask.shape)}")
+    # (every buffer the sampler owns is settled before the inversion captures: a new one drops the shape's graphs)
+    self._alloc_state(B, h, w, c)
+    self._owned("_mask_buf", mask, (B, h, w))
+    if self._de_qcoef is None:
+      self._de_qcoef = torch.tensor([[0., 1.]] * n, dtype=torch.float32, device=self.device).contiguous()
+    noise_table = self._eta_noise_table(noises, seed, first_sample_index, B, h, w, c)
+    self.ddim_invert_loop(source_inputs, latents=z0, guidance_scale=invert_guidance_scale, strength=strength,
+                          trajectory=True)
+    context = self._cond_stage_model(target_inputs)
+    self._set_context(context)
+    start = self._traj[k - 1]
+
+    def set_start():
+      self._xt.copy_(start)
+      self._x2[:B].copy_(start)
+      self._x2[B:].copy_(start)
+
+    self._blend_traj = True
+    try:
+      return self._denoise(k, set_start, guidance_scale, None, noise_table, True, False, record)
+    finally:
+      self._blend_traj = False
 
   # ---- panorama (DESIGN.md section 12) ---------------------------------------------------------
   def _alloc_windows(self, B, n_win, h, w, c):

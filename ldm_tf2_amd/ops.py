@@ -21,7 +21,8 @@ __all__ = [
     "bmm_nt", "conv3x3_small", "groupnorm", "layernorm", "softmax_rows", "attention",
     "time_embedding", "gemv", "cfg_ddim_update", "cfg_ddim_update_masked", "cfg_plms_update", "q_sample",
     "philox_u32", "normal_fill", "q_sample_rng", "cfg_ddim_update_rng", "cfg_plms_update_rng", "cfg_ms_update",
-    "cfg_ms_update_rng", "cfg_sched_update", "cfg_ddim_invert_update", "window_gather", "window_fold", "window_gather_ex", "window_fold_ex", "wrap_pad", "resize_nhwc", "resample_nhwc", "latent_preview", "xattn_map", "xattn_map_supported", "post_quant", "vq_nearest", "embedding",
+    "cfg_ms_update_rng", "cfg_sched_update", "cfg_ddim_invert_update", "window_gather", "window_fold", "window_gather_ex", "window_fold_ex", "wrap_pad", "resize_nhwc", "resample_nhwc", "latent_preview", "xattn_map", "xattn_map_supported",
+    "eps_contrast_accum", "contrast_mask", "contrast_mask_supported", "store_row", "post_quant", "vq_nearest", "embedding",
     "minmax_u8", "cast",
 ]
 
@@ -1233,6 +1234,53 @@ def xattn_map(q, k, acc, heads, s, sp, log2_scale, step_w=None, index=None, inde
                           int(heads), T, Tk, int(s), int(sp), float(log2_scale), code(q.dtype), _ptr(step_w), n_w,
                           _ptr(index), int(index_bias), _stream()), "ldm_xattn_map")
   return acc
+
+
+def eps_contrast_accum(eps_all, acc, counter=None):
+  """DiffEdit's contrast accumulator (include/ldm_hip.h, DESIGN.md section 19): eps_all [2B,...,c] float32 = [e_src;
+  e_tgt], acc [B,...] float32 (one value per cell) += sum_j |e_tgt[j] - e_src[j]| in float32, j ascending.  `counter`
+  (a device int32 tensor): decremented by one after the launch has read everything.  Any view of contiguous memory
+  passes; c = 4 needs both 16-byte aligned."""
+  assert eps_all.is_contiguous() and acc.is_contiguous(), (eps_all.stride(), acc.stride())
+  assert eps_all.dim() >= 2 and eps_all.shape[0] % 2 == 0, tuple(eps_all.shape)
+  B, c = int(eps_all.shape[0]) // 2, int(eps_all.shape[-1])
+  assert B >= 1 and acc.shape[0] == B and acc.numel() * c * 2 == eps_all.numel(), (tuple(eps_all.shape), tuple(acc.shape))
+  if counter is not None:
+    assert counter.dtype == torch.int32 and counter.numel() >= 1
+  check(lib.ldm_eps_contrast_accum(_ptr(_f32(eps_all, "eps_all")), _ptr(_f32(acc, "acc")), _ptr(counter), B,
+                                   acc.numel() // B, c, _stream()), "ldm_eps_contrast_accum")
+  return acc
+
+
+def contrast_mask_supported(h, w, dilate=0):
+  """Whether ldm_contrast_mask takes this shape (h w <= 65536, dilate in 0..3)."""
+  return bool(lib.ldm_contrast_mask_supported(int(h), int(w), int(dilate)))
+
+
+def contrast_mask(acc, mask_out, tau, dilate=0, mean_out=None, thr_out=None, count_out=None):
+  """DiffEdit's mask (include/ldm_hip.h): acc [B,h,w] float32 -> mask_out [B,h,w] float32, 1 =
+  keep: edit = acc > tau * mean of the sample, dilated by `dilate` cells, mask = 1 - edit.  mean_out, thr_out float32
+  [B] and count_out int32 [B] (the edited cells) are optional."""
+  assert acc.dim() == 3 and acc.is_contiguous(), (tuple(acc.shape), acc.stride())
+  B, h, w = (int(v) for v in acc.shape)
+  assert mask_out.is_contiguous() and tuple(mask_out.shape) == (B, h, w), (tuple(mask_out.shape), (B, h, w))
+  for t, dt in ((mean_out, torch.float32), (thr_out, torch.float32), (count_out, torch.int32)):
+    assert t is None or (t.dtype == dt and t.is_contiguous() and t.numel() == B), (t.dtype, tuple(t.shape), B)
+  check(lib.ldm_contrast_mask(_ptr(_f32(acc, "acc")), _ptr(_f32(mask_out, "mask_out")), _ptr(mean_out), _ptr(thr_out),
+                              _ptr(count_out), B, h, w, float(tau), int(dilate), _stream()), "ldm_contrast_mask")
+  return mask_out
+
+
+def store_row(src, table, index, index_sign=1, index_bias=0):
+  """table[index_sign * index[0] + index_bias] = src (float32; `index` a device int32 tensor): the inverse of
+  select_row.  A row outside the table writes nothing.  table [rows,...] with the rows `src.numel()` floats or more
+  apart."""
+  assert src.is_contiguous() and table.dim() >= 2 and table[0].is_contiguous() and table[0].numel() == src.numel(), \
+      (tuple(src.shape), tuple(table.shape), table.stride())
+  assert index.dtype == torch.int32 and index.numel() >= 1
+  check(lib.ldm_store_row(_ptr(_f32(src, "src")), _ptr(_f32(table, "table")), table.stride(0), table.shape[0],
+                          _ptr(index), int(index_sign), int(index_bias), src.numel(), _stream()), "ldm_store_row")
+  return table
 
 
 def post_quant(latents, scale_factor, kernel_io, bias, out):

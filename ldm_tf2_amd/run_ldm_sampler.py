@@ -55,6 +55,14 @@ default 1) and sampled back under `text_prompt`, the targe
 prompt twice with both scales 1 reconstructs the image.  `mask`, `window` and `sample_save_progress` cannot be combined
 with it.  Without `source_prompt` nothing changes.
 
+DiffEdit: optional `ldm_sampling` key `edit_mask: auto` (needs `source_prompt` and `init_image`).
+The edit stays inside a mask estimated from the two prompts: `edit_mask_maps` (default 10) noise draws at
+`edit_mask_strength` (default 0.5) of the schedule give a map of where the prompts' noise predictions differ, cells
+above `edit_mask_threshold` (0.5) times `edit_mask_clamp_ratio` (3.0) times the map's mean are edited, grown by
+`edit_mask_dilate` (0..3, default 0) cells, and every other cell follows the image's own inversion.  Each of the five
+keys needs `edit_mask`; `guidance_interval` and a list `guidance_scale` cannot be combined with it.  Without `edit_mask`
+nothing changes.
+
 Two-pass high resolution ("hires fix"): optional `ldm_sampling` keys `hires_shape: [B, H, W, c]`, `hires_strength`
 (default 0.5) and `hires_resize` (`nearest`, `bilinear` (default) or `bicubic`).  With `hires_shape`, `latent_shape` is
 sampled as usual, the latents are resized to `hires_shape` on the device and the last `int(hires_strength * N)` DDIM
@@ -307,7 +315,61 @@ def edit_call(config, token_ids, source_ids, seed):
   kwargs = dict(strength=float(samp.get("strength", 0.75)),
                 invert_guidance_scale=float(samp.get("invert_guidance_scale", 1.)), seed=seed,
                 **guidance_kwargs(config), **init_fit_kwargs(config))
+  em = edit_mask_kwargs(config)
+  if em is not None:
+    return ("ddim_p_sample_loop_diffedit", (source_ids, token_ids, _init_images(samp), samp["guidance_scale"]),
+            dict(kwargs, **em))
   return "ddim_p_sample_loop_edit", (source_ids, token_ids, _init_images(samp), samp["guidance_scale"]), kwargs
+
+
+# `edit_mask_*` key -> (the DiffEdit loop's keyword, its type)
+EDIT_MASK_KEYS = {"edit_mask_strength": ("mask_strength", float), "edit_mask_maps": ("num_maps", int),
+                  "edit_mask_threshold": ("mask_threshold", float), "edit_mask_clamp_ratio": ("mask_clamp_ratio", float),
+                  "edit_mask_dilate": ("mask_dilate", int)}
+
+
+def edit_mask_kwargs(config):
+  """`ldm_sampling.edit_mask: auto` with `edit_mask_strength` / `edit_mask_maps` / `edit_mask_threshold` /
+  `edit_mask_clamp_ratio` / `edit_mask_dilate` (the reference's YAML has no such keys), checked:
+  None without `edit_mask`, else the DiffEdit loop's mask keywords (those of the keys given; the loop has the
+  defaults).  The mask belongs to the prompt edit with one float guidance scale."""
+  samp = config["ldm_sampling"]
+  on = samp.get("edit_mask")
+  if on is None:
+    for key in EDIT_MASK_KEYS:
+      if samp.get(key) is not None:
+        raise ValueError(f"ldm_sampling.{key} needs ldm_sampling.edit_mask")
+    return None
+  if on != "auto":
+    raise ValueError(f"ldm_sampling.edit_mask must be 'auto', got {on!r}")
+  for key in ("source_prompt", "init_image"):
+    if not samp.get(key):
+      raise ValueError(f"ldm_sampling.edit_mask needs ldm_sampling.{key}")
+  if samp.get("guidance_interval") is not None:
+    raise ValueError("ldm_sampling.edit_mask cannot be combined with ldm_sampling.guidance_interval")
+  if np.ndim(samp["guidance_scale"]) > 0:
+    raise ValueError("ldm_sampling.edit_mask cannot be combined with a list ldm_sampling.guidance_scale")
+  out = {}
+  for key, (name, kind) in EDIT_MASK_KEYS.items():
+    v = samp.get(key)
+    if v is None:
+      continue
+    ok = isinstance(v, int) and not isinstance(v, bool) if kind is int else \
+        isinstance(v, (int, float)) and not isinstance(v, bool)
+    if not ok:
+      raise ValueError(f"ldm_sampling.{key} must be {'an int' if kind is int else 'a number'}, got {v!r}")
+    out[name] = kind(v)
+  if "num_maps" in out and out["num_maps"] < 1:
+    raise ValueError(f"ldm_sampling.edit_mask_maps must be at least 1, got {out['num_maps']!r}")
+  if "mask_dilate" in out and not 0 <= out["mask_dilate"] <= 3:
+    raise ValueError(f"ldm_sampling.edit_mask_dilate must be in [0, 3], got {out['mask_dilate']!r}")
+  if "mask_strength" in out and not 0. < out["mask_strength"] <= 1.:
+    raise ValueError(f"ldm_sampling.edit_mask_strength must be in (0, 1], got {out['mask_strength']!r}")
+  for key in ("edit_mask_threshold", "edit_mask_clamp_ratio"):
+    name = EDIT_MASK_KEYS[key][0]
+    if name in out and not (np.isfinite(out[name]) and out[name] >= 0.):
+      raise ValueError(f"ldm_sampling.{key} must be finite and not negative, got {out[name]!r}")
+  return out
 
 
 PREVIEW_KEYS = ("preview_scale", "preview_mode", "preview_matrix")
@@ -418,6 +480,7 @@ def sampling_call(config, token_ids, seed, source_ids=None):
   init_fit_kwargs(config)                        # (ValueError: an unknown init_fit or init_filter, whatever the loop)
   preview = preview_kwargs(config)               # (ValueError: a loop without previews, or a key without preview_freq)
   preview.update(attention_map_kwargs(config))   # (the heat maps go where the previews go, and refuse the same loops)
+  edit_mask_kwargs(config)                       # (ValueError: a key without edit_mask, edit_mask without its prompt)
   for key in PANORAMA_WRAP_KEYS:
     if samp.get(key) is not None and samp.get("window") is None:
       raise ValueError(f"ldm_sampling.{key} needs ldm_sampling.window")
