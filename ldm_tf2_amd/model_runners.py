@@ -75,6 +75,7 @@ slots of their own; without the keywords every key, launch and graph is the one 
 """
 from __future__ import annotations
 
+import itertools
 import sys
 
 import numpy as np
@@ -98,6 +99,11 @@ def _tf_linspace_f32(start, stop, num):
 def _extract(data, t):
   """model_runners.py:28-45: cast to float32 THEN gather; shape [-1,1,1,1]."""
   return np.asarray(data).astype(np.float32)[np.asarray(t)].reshape(-1, 1, 1, 1)
+
+
+def _as_tensor(x, dtype=torch.float32):
+  """A caller's array (a tensor, a NumPy array or nested numbers) as a tensor of `dtype` (None: its own), where it is."""
+  return torch.as_tensor(x if isinstance(x, torch.Tensor) else np.asarray(x), dtype=dtype)
 
 
 def normal_latents(seed, first_index, count, shape_hwc, stream=None):
@@ -570,7 +576,7 @@ class LatentDiffusionModel(object):
     _extract(sqrt_1m_ac, t) * eps.  x0, eps [B,h,w,c]; t int [B] DDPM timesteps.  float32, on the device."""
     x0 = torch.as_tensor(x0, dtype=torch.float32).to(self.device).contiguous()
     eps = torch.as_tensor(eps, dtype=torch.float32).to(self.device).contiguous()
-    t = torch.as_tensor(np.asarray(t) if not isinstance(t, torch.Tensor) else t).to(self.device, torch.int32)
+    t = _as_tensor(t, dtype=None).to(self.device, torch.int32)
     t = t.reshape(-1).contiguous()
     if tuple(eps.shape) != tuple(x0.shape) or t.numel() != x0.shape[0]:
       raise ValueError(f"q_sample: x0 {tuple(x0.shape)}, eps {tuple(eps.shape)}, t {tuple(t.shape)}")
@@ -593,8 +599,7 @@ class LatentDiffusionModel(object):
                                 self._set_rng(seed, first_sample_index), ENCODE_STREAM)
       elif noise is None:
         noise = normal_latents(seed, first_sample_index, B, (h, w, c2 // 2), stream=ENCODE_STREAM)
-      noise = torch.as_tensor(np.asarray(noise) if not isinstance(noise, torch.Tensor) else noise,
-                              dtype=torch.float32).to(self.device).contiguous()
+      noise = _as_tensor(noise).to(self.device).contiguous()
       if tuple(noise.shape) != (B, h, w, c2 // 2):
         raise ValueError(f"encode noise {tuple(noise.shape)} != latents {(B, h, w, c2 // 2)}")
       out = torch.empty(B, h, w, c2 // 2, dtype=torch.float32, device=moments.device)
@@ -690,38 +695,21 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     self._skip_unguided = bool(skip_unguided)    # A/B: False = an unguided step still evaluates all 2B rows
     self._states = {}                            # (B,h,w,c) -> the device state and captured graphs of a shape
     self._state_key = None                       # that is not the current one (_alloc_state)
-    self._graph = None
-    self._graph_key = None
-    self._sched_graphs = {}                      # guidance schedules: form (guided?) -> captured step
-    self._sched_key = None
+    for slot, (key, by_form) in self._GRAPH_SLOTS.items():
+      setattr(self, slot, {} if by_form else None)
+      setattr(self, key, None)
     self._gtab = None
     self._plms_tbl = None
     self._form_events = None
-    self._inv_graph = None                       # the inversion's captured step: it coexists
-    self._inv_graph_key = None                   # with the sampling graphs above
     self._inv_tbl = None
     self._inv_temb = None
-    self._pv_graph = None                        # the steps captured with previews have slots
-    self._pv_graph_key = None                    # of their own: a loop without previews finds its graph as it left it
-    self._pv_sched_graphs = {}
-    self._pv_sched_key = None
     self._pv_proj = None                         # set_preview: the matrix on the device, the scale and the mode
     self._pv_host = None
     self._pv_scale = None
     self._pv_mode = "bilinear"
     self._pv_last = None
-    self._am_graph = None                        # the steps captured with heat maps: a slot of
-    self._am_graph_key = None                    # their own too
     self._am_tab = None                          # the weights by DDIM index on the device (values change in place)
     self._am_last = None
-    # DiffEdit: the contrast step, the inversion that keeps its trajectory and the sampling
-    # whose blend reads it are captured in slots of their own, beside every graph above
-    self._dm_graph = None
-    self._dm_graph_key = None
-    self._invt_graph = None
-    self._invt_graph_key = None
-    self._de_graph = None
-    self._de_graph_key = None
     self._dm_counters = None                     # two device ints: the contrast step's DDIM index, its draw counter
     self._de_qcoef = None                        # the blend's constant coefficients (0, 1): q_sample(z0, Q) = Q
     self._blend_traj = False                     # whether _blend_kwargs hands the blend the trajectory for Q
@@ -754,9 +742,23 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
   _SHAPE_BUFFERS = ("_xt", "_x2", "_eps", "_ring", "_start", "_noise_buf", "_q_buf", "_z0_buf", "_mask_buf", "_t_buf",
                     "_x_win", "_eps_win", "_win_key", "_win_wy", "_win_wx", "_pv_x0", "_pv_a", "_pv_b", "_am_accs",
                     "_traj", "_dm_acc", "_dm_out", "_dm_noise", "_dm_t")
-  _SHAPE_GRAPHS = ("_graph", "_graph_key", "_sched_graphs", "_sched_key", "_inv_graph", "_inv_graph_key",
-                   "_pv_graph", "_pv_graph_key", "_pv_sched_graphs", "_pv_sched_key", "_am_graph", "_am_graph_key",
-                   "_dm_graph", "_dm_graph_key", "_invt_graph", "_invt_graph_key", "_de_graph", "_de_graph_key")
+  # The captured-graph slots, declared once: attribute -> (the attribute of its key, by_form).  A slot holds one
+  # captured step (_sample_loop), or with by_form a dict form (guided?) -> captured step (_sample_loop_sched), and the
+  # key says what it was captured for.  A loop with a slot of its own (`slot=`) finds the others' graphs as it left
+  # them.  The defaults of a fresh sampler, what travels with a shape (_SHAPE_GRAPHS), the keys a fresh shape resets
+  # and what _drop_graphs / _clear_slots empty all derive from this table: a new slot is one entry here.
+  _GRAPH_SLOTS = {
+      "_graph": ("_graph_key", False),               # the sampling loops without a slot of their own
+      "_sched_graphs": ("_sched_key", True),         # guidance schedules
+      "_inv_graph": ("_inv_graph_key", False),       # the inversion's step (section 13)
+      "_pv_graph": ("_pv_graph_key", False),         # the steps captured with previews (section 17)
+      "_pv_sched_graphs": ("_pv_sched_key", True),
+      "_am_graph": ("_am_graph_key", False),         # the steps captured with heat maps (section 18)
+      "_dm_graph": ("_dm_graph_key", False),         # DiffEdit (section 19): the contrast step,
+      "_invt_graph": ("_invt_graph_key", False),     # the inversion that keeps its trajectory
+      "_de_graph": ("_de_graph_key", False),         # and the sampling whose blend reads it
+  }
+  _SHAPE_GRAPHS = tuple(_GRAPH_SLOTS) + tuple(key for key, _ in _GRAPH_SLOTS.values())
 
   def _alloc_state(self, B, h, w, c):
     key = (B, h, w, c)
@@ -773,8 +775,8 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
           setattr(self, n, v)
         self._state_key = key
         return
-      self._graph_key = self._sched_key = self._inv_graph_key = self._pv_graph_key = self._pv_sched_key = None
-      self._am_graph_key = self._dm_graph_key = self._invt_graph_key = self._de_graph_key = None
+      for slot_key, _ in self._GRAPH_SLOTS.values():
+        setattr(self, slot_key, None)
       dev, f32 = self.device, torch.float32
       self._xt = torch.empty(B, h, w, c, dtype=f32, device=dev)
       self._x2 = torch.empty(2 * B, h, w, c, dtype=f32, device=dev)
@@ -797,13 +799,16 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
 
   def _drop_graphs(self):
     """A buffer the captured steps of the current shape read has a new address."""
-    self._graph = None
-    self._sched_graphs = {}
-    self._inv_graph = None
-    self._pv_graph = None
-    self._pv_sched_graphs = {}
-    self._am_graph = None
-    self._dm_graph = self._invt_graph = self._de_graph = None
+    self._clear_slots(*self._GRAPH_SLOTS)
+
+  def _clear_slots(self, *slots, all_shapes=False):
+    """Empties the named slots of the current shape and, with `all_shapes`, of every shape parked in _states: what
+    their captured steps read is gone.  The keys stay (a key without its graph matches nothing)."""
+    for slot in slots:
+      by_form = self._GRAPH_SLOTS[slot][1]
+      setattr(self, slot, {} if by_form else None)
+      for saved in self._states.values() if all_shapes else ():
+        saved[slot] = {} if by_form else None
 
   # ---- latent previews (DESIGN.md section 17) --------------------------------------------------
   def set_preview(self, proj, scale=None, mode="bilinear"):
@@ -829,9 +834,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     self._pv_host = proj.copy()
     self._pv_proj = torch.from_numpy(self._pv_host).to(self.device).contiguous()
     self._pv_scale, self._pv_mode = int(scale), mode
-    self._pv_graph, self._pv_sched_graphs = None, {}
-    for saved in self._states.values():
-      saved.update({"_pv_graph": None, "_pv_sched_graphs": {}})
+    self._clear_slots("_pv_graph", "_pv_sched_graphs", all_shapes=True)
 
   def fit_preview(self, latents=None, n=8, seed=0, shape=None):
     """Fits the previews' matrix on this sampler's own decoder and stores it (set_preview, keeping the scale and mode
@@ -850,8 +853,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
           side = getattr(self._autoencoder, "_latent_size", None) or 32
           shape = (side, side, getattr(self._autoencoder, "_latent_channels", 4))
       latents = normal_latents(seed, 0, int(n), tuple(int(v) for v in shape), stream=PREVIEW_FIT_STREAM)
-    lat = torch.as_tensor(np.asarray(latents) if not isinstance(latents, torch.Tensor) else latents,
-                          dtype=torch.float32).to(self.device).contiguous()
+    lat = _as_tensor(latents).to(self.device).contiguous()
     images = self.decode_first_stage(lat)
     proj = fit_latent_preview(lat, images)
     self.set_preview(proj, scale=self._pv_scale, mode=self._pv_mode)
@@ -878,7 +880,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       self._pv_x0 = torch.empty(B, h, w, c, dtype=torch.float32, device=self.device)
       self._pv_a = torch.zeros(shape, dtype=torch.uint8, device=self.device)
       self._pv_b = torch.zeros(shape, dtype=torch.uint8, device=self.device)
-      self._pv_graph, self._pv_sched_graphs = None, {}           # (the captured launches wrote the old strips)
+      self._clear_slots("_pv_graph", "_pv_sched_graphs")         # (the captured launches wrote the old strips)
     return q
 
   def _preview_step(self, q, dec_index):
@@ -929,9 +931,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       raise ValueError(f"attn_layers must be distinct indices below {n_st}, got {attn_layers!r}")
     if self._am_tab is None or self._am_tab.numel() != len(w):
       self._am_tab = torch.empty(len(w), dtype=torch.float32, device=self.device)
-      self._am_graph = None
-      for saved in self._states.values():
-        saved.update({"_am_graph": None})
+      self._clear_slots("_am_graph", all_shapes=True)
     self._am_tab.copy_(torch.from_numpy(w))
     return w, layers
 
@@ -972,10 +972,22 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     if self._sampler in MULTISTEP:
       self._start.fill_(int(start_index))
 
+  def _start_counters(self, k):
+    """The device counters of a sampling loop whose first step is the one at DDIM index k - 1."""
+    self._index_dev.fill_(self._loop_start_index(k))                      # :476 (index = k - 1 in the first step)
+    self._set_loop_start(k - 1)
+
+  def _copy_start(self, src):
+    """A loop's start state from latents on the device: _xt and both halves of the first U-Net input."""
+    B = self._xt.shape[0]
+    self._xt.copy_(src)
+    self._x2[:B].copy_(src)
+    self._x2[B:].copy_(src)
+
   def _owned(self, name, src, shape, dtype=torch.float32):
     """`src` copied into a buffer the sampler owns (one per name and shape): a captured graph reads it at a
     fixed address, whatever tensor the caller passed.  A new buffer drops the captured graph."""
-    src = torch.as_tensor(np.asarray(src) if not isinstance(src, torch.Tensor) else src, dtype=dtype)
+    src = _as_tensor(src, dtype)
     if tuple(src.shape) != tuple(shape):
       raise ValueError(f"{name}: shape {tuple(src.shape)}, expected {tuple(shape)}")
     buf = getattr(self, name, None)
@@ -1092,51 +1104,24 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
                          dec_index=dec_index and not self._pre_dec, pred_x0_out=pred_x0_out, **hist,
                          **self._blend_kwargs(masked, rng))
 
-  def _sample_loop_sched(self, forms, reset, step, gkey, record, slot="_sched", after_step=None):
+  def _sample_loop_sched(self, forms, reset, step, gkey, record, slot="_sched_graphs", after_step=None):
     """_sample_loop for a guidance schedule: forms[s] = whether the s-th step of the loop is guided (host-known when
     the loop starts; the index stays on the device); `step(guided, dec_index)` enqueues one step.  With graphs, one
-    step per form in use is captured once per `gkey` and the host replays whichever form each step takes.  Events
-    around every contiguous run of one form give the per-form times (last_form_ms_per_step).  `slot`: the attributes
-    that keep the graphs and their key (`slot`_graphs, `slot`_key), as in _sample_loop; `after_step(s)` runs on the
-    host after the s-th step is enqueued."""
-    num_steps = len(forms)
+    step per form in use is captured once per `gkey` (guided first) and the host replays whichever form each step
+    takes.  Events around every contiguous run of one form give the per-form times (last_form_ms_per_step).  `slot`:
+    a by-form slot of _GRAPH_SLOTS, as in _sample_loop; `after_step(s)` runs on the host after the s-th step is
+    enqueued."""
     reset()
-    use_graph = self._use_graph and record is None
-    if use_graph:
-      if getattr(self, slot + "_key") != gkey:
-        setattr(self, slot + "_graphs", {})
-        setattr(self, slot + "_key", gkey)
-      graphs = getattr(self, slot + "_graphs")
+    graphs = None
+    if self._use_graph and record is None:
+      key = self._GRAPH_SLOTS[slot][0]
+      if getattr(self, key) != gkey:
+        self._clear_slots(slot)
+        setattr(self, key, gkey)
+      graphs = getattr(self, slot)
       for guided in sorted(set(forms) - set(graphs), reverse=True):
-        self._index_dev.fill_(num_steps - 1)         # (the warm-up step does not move the counter)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-          step(guided, False)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        reset()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-          step(guided, True)
-        graphs[guided] = g
-        reset()
-    marks = [(torch.cuda.Event(enable_timing=True), None)]
-    marks[0][0].record()
-    for i, guided in enumerate(forms):
-      if use_graph:
-        graphs[guided].replay()
-      else:
-        step(guided, True)
-        if record is not None:
-          record.append(self._xt.clone())
-      if after_step is not None:
-        after_step(i)
-      if i + 1 == num_steps or forms[i + 1] != guided:
-        ev = torch.cuda.Event(enable_timing=True)
-        ev.record()
-        marks.append((ev, guided))
-    self._loop_events = (marks[0][0], marks[-1][0], num_steps)
+        graphs[guided] = self._capture_step(len(forms), reset, lambda dec: step(guided, dec))
+    marks = self._run_steps(forms, graphs, step, record, after_step)
     self._form_events = (marks, list(forms))
 
   def last_form_ms_per_step(self):
@@ -1167,9 +1152,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     B, h, w, c = xt.shape
     self._alloc_state(B, h, w, c)
     self._set_context(cond)
-    self._xt.copy_(xt)
-    self._x2[:B].copy_(xt)
-    self._x2[B:].copy_(xt)
+    self._copy_start(xt)
     self._index_dev.fill_(int(index))
     nz = None
     if noise is not None:
@@ -1229,47 +1212,63 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     _loop_start_index(num_steps)); `step(dec_index)` enqueues one step.  With graphs (and no `record`) one step
     is captured once per `gkey` -- after a warm-up step on a side stream has allocated every scratch buffer --
     and replayed num_steps times; the counter lives on the device, so the graph serves any start index.  `slot`: the
-    attribute that keeps the graph (its key in `slot`_key): a loop with a slot of its own does not evict the others'.
+    slot of _GRAPH_SLOTS that keeps the graph and its key: a loop with a slot of its own does not evict the others'.
     `after_step(s)` runs on the host after the s-th step is enqueued."""
     reset()
-    use_graph = self._use_graph and record is None
-    t0 = torch.cuda.Event(enable_timing=True)
-    t1 = torch.cuda.Event(enable_timing=True)
-    if use_graph:
-      if getattr(self, slot) is None or getattr(self, slot + "_key") != gkey:
-        self._index_dev.fill_(num_steps - 1)         # (the warm-up step does not move the counter)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-          step(False)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        reset()
-        g = torch.cuda.CUDAGraph()
-        # thread-local capture mode: in a multi-GPU job the RCCL watchdog thread polls events
-        # while this thread captures; only this thread's calls belong to the capture
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-          step(True)
-        setattr(self, slot, g)
-        setattr(self, slot + "_key", gkey)
-        reset()
-      graph = getattr(self, slot)
-      t0.record()
-      for i in range(num_steps):                                          # :484-502
-        graph.replay()
+    graphs = None
+    if self._use_graph and record is None:
+      key = self._GRAPH_SLOTS[slot][0]
+      if getattr(self, slot) is None or getattr(self, key) != gkey:
+        setattr(self, slot, self._capture_step(num_steps, reset, step))
+        setattr(self, key, gkey)
+      graphs = {None: getattr(self, slot)}
+    self._run_steps([None] * num_steps, graphs, lambda form, dec: step(dec), record, after_step)      # :484-502
+
+  def _capture_step(self, num_steps, reset, step):
+    """The graph of one step `step(dec_index)`, captured from the state `reset()` sets after a warm-up step on a side
+    stream has allocated every scratch buffer; leaves that state behind.  The one capture sequence of every loop."""
+    self._index_dev.fill_(num_steps - 1)             # (the warm-up step does not move the counter)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+      step(False)
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    reset()
+    g = torch.cuda.CUDAGraph()
+    # thread-local capture mode: in a multi-GPU job the RCCL watchdog thread polls events
+    # while this thread captures; only this thread's calls belong to the capture
+    with torch.cuda.graph(g, capture_error_mode="thread_local"):
+      step(True)
+    reset()
+    return g
+
+  def _run_steps(self, forms, graphs, step, record, after_step):
+    """The timed run of every loop: step s takes the form forms[s] -- a replay of graphs[form], or with `graphs` None
+    the eager `step(form, True)`, after which `record` receives a copy of x_t -- and `after_step(s)` follows it on the
+    host.  An event is recorded right before the first step and after the last step of every contiguous run of one
+    form; returns them as [(event, the form of the run it ends)] (None for the first) and sets _loop_events."""
+    runs = [(form, len(list(same))) for form, same in itertools.groupby(forms)]
+    marks = [(torch.cuda.Event(enable_timing=True), None)]
+    done = 0
+    marks[0][0].record()
+    for form, count in runs:
+      replay = None if graphs is None else graphs[form].replay
+      for i in range(done, done + count):
+        if replay is not None:
+          replay()
+        else:
+          step(form, True)
+          if record is not None:
+            record.append(self._xt.clone())
         if after_step is not None:
           after_step(i)
-      t1.record()
-    else:
-      t0.record()
-      for i in range(num_steps):
-        step(True)
-        if record is not None:
-          record.append(self._xt.clone())
-        if after_step is not None:
-          after_step(i)
-      t1.record()
-    self._loop_events = (t0, t1, num_steps)
+      done += count
+      ev = torch.cuda.Event(enable_timing=True)
+      ev.record()
+      marks.append((ev, form))
+    self._loop_events = (marks[0][0], marks[-1][0], len(forms))
+    return marks
 
   def _denoise(self, k, set_start, guidance_scale, gsched, noise_table, masked, rng, record, decode=True,
                preview_freq=None, on_preview=None, attn_maps=None, attn_layers=None):
@@ -1287,9 +1286,8 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
 
     def reset():
       set_start()
-      self._index_dev.fill_(self._loop_start_index(k))                    # :476 (index = k - 1 in the first step)
-      self._set_loop_start(k - 1)
-      if q is not None:                        # (outside the graph: what the warm-up and capture steps wrote goes,
+      self._start_counters(k)
+      if q is not None:                       # (outside the graph: what the warm-up and capture steps wrote goes,
         self._pv_a.zero_()                     # and the slots this loop never reaches read 0)
         self._pv_b.zero_()
       if am is not None:                       # (outside the graph too: the warm-up and capture steps added theirs)
@@ -1309,7 +1307,8 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       pkey, own = (("traj_blend",),), dict(slot="_de_graph")
     if q is not None:
       pv, pkey = dict(pred_x0_out=self._pv_x0), (("preview", q, self._pv_scale, self._pv_mode),)
-      own, own_sched = dict(slot="_pv_graph", after_step=after_step), dict(slot="_pv_sched", after_step=after_step)
+      own = dict(slot="_pv_graph", after_step=after_step)
+      own_sched = dict(slot="_pv_sched_graphs", after_step=after_step)
       self._pv_last = (q, k, self._pv_a, self._pv_b)
 
     def step_sched(guided, dec):
@@ -1325,25 +1324,25 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     if gsched is not None:
       self._sample_loop_sched(self._sched_forms(gsched, k - 1, k), reset, step_sched,
                               self._sched_key_of(masked, rng) + pkey, record, **own_sched)
-      return self._finish(self._xt) if decode else self._xt
-    gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, masked, self._noise_source, rng,
-            self._step_spacing, self._sampler) + pkey
-    if am is not None:
-      # the conditional half of every evaluation, weighted by the table's entry at the device counter: inside the
-      # U-Net the counter holds the step's DDIM index in every mode (the temb launch has pre-decremented it, or the
-      # update moves it afterwards; the uncounted warm-up step sits on the loop's first index), so the bias is 0
-      self._unet.capture_attention(rows=(B, 2 * B), layers=am[1], step_w=self._am_tab, index_bias=0)
-      try:
-        self._sample_loop(k, reset, step, gkey + (("attn", am[1]),), record, slot="_am_graph")
-        fresh = self._unet.attention_layers()
-      finally:
-        self._unet.capture_attention(None)
-      if fresh:                                # (a replayed graph ran no host code: the accumulators are the ones
-        am_accs[am[1]] = fresh                 # its capture saw)
-        self._am_accs = am_accs
-      self._am_last = (float(am[0][:k].astype(np.float64).sum()), tuple(self._xt.shape[1:3]), am_accs[am[1]])
-      return self._finish(self._xt) if decode else self._xt
-    self._sample_loop(k, reset, step, gkey, record, **own)
+    else:
+      gkey = (float(guidance_scale), noise_table is not None, self._ctx_shape, masked, self._noise_source, rng,
+              self._step_spacing, self._sampler) + pkey
+      if am is None:
+        self._sample_loop(k, reset, step, gkey, record, **own)
+      else:
+        # the conditional half of every evaluation, weighted by the table's entry at the device counter: inside the
+        # U-Net the counter holds the step's DDIM index in every mode (the temb launch has pre-decremented it, or the
+        # update moves it afterwards; the uncounted warm-up step sits on the loop's first index), so the bias is 0
+        self._unet.capture_attention(rows=(B, 2 * B), layers=am[1], step_w=self._am_tab, index_bias=0)
+        try:
+          self._sample_loop(k, reset, step, gkey + (("attn", am[1]),), record, slot="_am_graph")
+          fresh = self._unet.attention_layers()
+        finally:
+          self._unet.capture_attention(None)
+        if fresh:                              # (a replayed graph ran no host code: the accumulators are the ones
+          am_accs[am[1]] = fresh               # its capture saw)
+          self._am_accs = am_accs
+        self._am_last = (float(am[0][:k].astype(np.float64).sum()), tuple(self._xt.shape[1:3]), am_accs[am[1]])
     return self._finish(self._xt) if decode else self._xt
 
   def ddim_p_sample_loop(self, cond_model_inputs, shape, guidance_scale=5., x_T=None,
@@ -1405,8 +1404,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       return None
     if x_T is None:
       x_T = normal_latents(seed, first_sample_index, B, (h, w, c))
-    xt = torch.as_tensor(np.asarray(x_T) if not isinstance(x_T, torch.Tensor) else x_T,
-                         dtype=torch.float32).to(self.device).contiguous()
+    xt = _as_tensor(x_T).to(self.device).contiguous()
     assert tuple(xt.shape) == (B, h, w, c)
     return xt
 
@@ -1418,9 +1416,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     if xt is None:
       ops.normal_fill(self._xt, self._rng, XT_STREAM, x_unet_out=self._x2)
       return
-    self._xt.copy_(xt)
-    self._x2[:B].copy_(xt)
-    self._x2[B:].copy_(xt)
+    self._copy_start(xt)
 
   def _finish(self, latents):
     if self._verbose:                                                     # :503
@@ -1464,9 +1460,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     if mask is not None and size is not None:
       mask = self._fit_mask(mask, tuple(imgs.shape[1:3]), size, fit)
     if mask is not None:
-      mask = torch.as_tensor(np.asarray(mask) if not isinstance(mask, torch.Tensor) else mask, dtype=torch.float32)
-      if mask.dim() == 2:
-        mask = mask[None].expand(B, *mask.shape)
+      mask = self._latent_mask(mask, B)
     if size is not None:
       imgs = self._fit_images(imgs, size, fit, resample)
     context = self._cond_stage_model(cond_model_inputs)
@@ -1481,9 +1475,8 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     (with the blend when `mask` is given), decode."""
     n = len(self._ddim_steps)
     B, h, w, c = z0.shape
-    if mask is not None and tuple(mask.shape) != (B, h, w):
-      raise ValueError(f"mask must be [B,h,w] = {(B, h, w)} (or [h,w]) at latent resolution, "
-                       f"got {tuple(mask.shape)}")
+    if mask is not None:
+      mask = self._latent_mask(mask, B, (h, w))
     self._alloc_state(B, h, w, c)
     self._set_context(context)
     rng = self._draws_on_device(noises, q_noises)
@@ -1592,13 +1585,24 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
 
   def _init_images(self, init_images, B):
     """init_images [B,H,W,3] (or [H,W,3], tiled over the batch) as a contiguous float32 tensor."""
-    imgs = torch.as_tensor(np.asarray(init_images) if not isinstance(init_images, torch.Tensor) else init_images,
-                           dtype=torch.float32)
+    imgs = _as_tensor(init_images)
     if imgs.dim() == 3:
       imgs = imgs[None].expand(B, *imgs.shape)
     if imgs.dim() != 4 or imgs.shape[0] != B or imgs.shape[-1] != 3:
       raise ValueError(f"init_images must be [B={B},H,W,3] or [H,W,3], got {tuple(imgs.shape)}")
     return imgs.contiguous()
+
+  @staticmethod
+  def _latent_mask(mask, B, hw=None):
+    """A latent mask [B,h,w] (or [h,w], tiled over the batch) as a float32 tensor; with `hw` = (h, w), the latents'
+    extents, checked against them."""
+    mask = _as_tensor(mask)
+    if mask.dim() == 2:
+      mask = mask[None].expand(B, *mask.shape)
+    if hw is not None and tuple(mask.shape) != (B, *hw):
+      raise ValueError(f"mask must be [B,h,w] = {(B, *hw)} (or [h,w]) at latent resolution, "
+                       f"got {tuple(mask.shape)}")
+    return mask
 
   # ---- init images and masks of any size (DESIGN.md section 15) ------------------------------
   def _pixel_factor(self):
@@ -1722,26 +1726,13 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     the launches, the graph and its key are what they were."""
     self._no_attn_maps(attn_maps, "the inversion loop")
     size = self._image_size(image_size, fit, resample)
-    if size is not None and init_images is None:
-      raise ValueError("image_size resamples init_images: it cannot be given with latents")
     if np.ndim(guidance_scale) > 0:
       raise ValueError("the inversion loop takes one float guidance_scale: a guidance schedule is not supported")
-    if (init_images is None) == (latents is None):
-      raise ValueError("ddim_invert_loop needs exactly one of init_images and latents")
     guidance_scale = float(guidance_scale)
     k = img2img_start(strength, len(self._ddim_steps))
     B = len(cond_model_inputs) // 2
+    z0 = self._edit_z0(init_images, latents, B, size, fit, resample, encode_noise, seed, first_sample_index)
     context = self._cond_stage_model(cond_model_inputs)
-    if latents is None:
-      imgs = self._init_images(init_images, B)
-      if size is not None:
-        imgs = self._fit_images(imgs, size, fit, resample)
-      z0 = self.get_latents(imgs, noise=encode_noise, seed=seed, first_sample_index=first_sample_index)
-    else:
-      z0 = torch.as_tensor(np.asarray(latents) if not isinstance(latents, torch.Tensor) else latents,
-                           dtype=torch.float32)
-      if z0.dim() != 4 or z0.shape[0] != B:
-        raise ValueError(f"latents must be [B={B},h,w,c], got {tuple(z0.shape)}")
     _, h, w, c = z0.shape
     self._alloc_state(B, h, w, c)
     self._set_context(context)
@@ -1749,9 +1740,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     self._invert_tables()                      # (made before any capture: the graph reads them at fixed addresses)
 
     def reset():
-      self._xt.copy_(z0_buf)
-      self._x2[:B].copy_(z0_buf)
-      self._x2[B:].copy_(z0_buf)
+      self._copy_start(z0_buf)
       self._index_dev.fill_(self._invert_counter_start())
 
     cond_only = guidance_scale == 1. and self._skip_unguided
@@ -1762,7 +1751,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       n = len(self._ddim_steps)
       if getattr(self, "_traj", None) is None:
         self._traj = torch.zeros(n, B, h, w, c, dtype=torch.float32, device=self.device)
-        self._invt_graph = self._de_graph = None
+        self._clear_slots("_invt_graph", "_de_graph")
 
       def step(dec):
         # after the update the counter holds N-1-j when the U-Net's first launch pre-decremented it and one less when
@@ -1842,7 +1831,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       return self.get_latents(imgs, noise=encode_noise, seed=seed, first_sample_index=first_sample_index)
     if size is not None:
       raise ValueError("image_size resamples init_images: it cannot be given with latents")
-    z0 = torch.as_tensor(np.asarray(latents) if not isinstance(latents, torch.Tensor) else latents, dtype=torch.float32)
+    z0 = _as_tensor(latents)
     if z0.dim() != 4 or z0.shape[0] != B:
       raise ValueError(f"latents must be [B={B},h,w,c], got {tuple(z0.shape)}")
     return z0
@@ -1893,8 +1882,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       if map_noises is None:
         map_noises = np.stack([normal_latents(seed, first_sample_index, B, (h, w, c), stream=MAP_STREAM + r)
                                for r in range(n)])
-      m = torch.as_tensor(np.asarray(map_noises) if not isinstance(map_noises, torch.Tensor) else map_noises,
-                          dtype=torch.float32)
+      m = _as_tensor(map_noises)
       if tuple(m.shape) != (n, B, h, w, c):
         raise ValueError(f"map_noises: shape {tuple(m.shape)}, expected {(n, B, h, w, c)}")
       buf = self._owned("_dm_noise", m.flip(0), (n, B, h, w, c))
@@ -1905,7 +1893,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
                       torch.empty(B, dtype=torch.float32, device=self.device),
                       torch.empty(B, dtype=torch.float32, device=self.device),
                       torch.empty(B, dtype=torch.int32, device=self.device))
-      self._dm_graph = None
+      self._clear_slots("_dm_graph")
     if self._dm_counters is None:
       self._dm_counters = torch.zeros(2, dtype=torch.int32, device=self.device)
     t_index, draw = self._dm_counters[0:1], self._dm_counters[1:2]
@@ -1975,12 +1963,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       mask = self._diffedit_mask(source_inputs, target_inputs, z0, k_m, n_maps, tau, dilate, map_noises, seed,
                                  first_sample_index)
     else:
-      mask = torch.as_tensor(np.asarray(mask) if not isinstance(mask, torch.Tensor) else mask, dtype=torch.float32)
-      if mask.dim() == 2:
-        mask = mask[None].expand(B, *mask.shape)
-      if tuple(mask.shape) != (B, h, w):
-        raise ValueError(f"mask must be [B,h,w] = {(B, h, w)} (or [h,w]) at latent resolution, "
-                         f"got {tuple(mask.shape)}")
+      mask = self._latent_mask(mask, B, (h, w))
     # (every buffer the sampler owns is settled before the inversion captures: a new one drops the shape's graphs)
     self._alloc_state(B, h, w, c)
     self._owned("_mask_buf", mask, (B, h, w))
@@ -1993,14 +1976,9 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     self._set_context(context)
     start = self._traj[k - 1]
 
-    def set_start():
-      self._xt.copy_(start)
-      self._x2[:B].copy_(start)
-      self._x2[B:].copy_(start)
-
     self._blend_traj = True
     try:
-      return self._denoise(k, set_start, guidance_scale, None, noise_table, True, False, record)
+      return self._denoise(k, lambda: self._copy_start(start), guidance_scale, None, noise_table, True, False, record)
     finally:
       self._blend_traj = False
 
@@ -2105,8 +2083,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
         ops.normal_fill(self._xt, self._rng, XT_STREAM)
       else:
         self._xt.copy_(xt)
-      self._index_dev.fill_(self._loop_start_index(n))
-      self._set_loop_start(n - 1)
+      self._start_counters(n)
 
     gkey = ("panorama", (B, H, W, c), (h, w), (sy, sx), float(guidance_scale), noise_table is not None,
             self._ctx_shape, False, self._noise_source, rng, self._step_spacing, self._sampler, wrap, profile)
@@ -2137,8 +2114,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     rng = self._draws_on_device(noises)
     noise_table = None if rng else self._eta_noise_table(noises, seed, first_sample_index, B, h, w, c)
     self._set_x_T(xt, seed, first_sample_index, B)
-    self._index_dev.fill_(self._loop_start_index(n))
-    self._set_loop_start(n - 1)
+    self._start_counters(n)
     sample_prog = torch.zeros(B, num_records, h, w, c, dtype=torch.float32, device=self.device)
     x0_prog = torch.zeros_like(sample_prog)
     pred_x0 = torch.empty_like(self._xt)
