@@ -52,8 +52,8 @@ extern "C" {
 #define LDM_ACT_GELU 1  /* exact erf gelu: transformer.py:169 (tf.nn.gelu)        */
 #define LDM_ACT_GEGLU 2 /* value*gelu(gate): unet.py:323-325; weight rows interleaved
                            in blocks of 64 = 32 value rows then their 32 gate rows.
-                           Tiles 0 (auto), 1, 2, 5, 11, 12, 14, 19.  Takes no addend
-                           (LDM_ERR_ARG).  On tiles 11 / 12 without split-K the output
+                           Tile 0 (auto) and the LDM_TILE_GEGLU ones.  Takes no addend
+                           (LDM_ERR_ARG).  On LDM_TILE_GEGLU_VEC tiles without split-K the output
                            must qualify for the 16-byte vector epilogue (out, bias and
                            residual 16-byte aligned, row pitches multiples of 8
                            elements), else LDM_ERR_ARG; the automatic plan (tile 0)
@@ -85,7 +85,7 @@ int ldm_last_error(char* buf, int n);
  *   w being [4][N][K = 4*Cin] with the 3x3 taps that fall on one image pixel summed beforehand
  *   (layout.upsample_phase_kernel): 4/9 of the multiply-adds.  Stride 1; M = B*2H*2W as with
  *   upsample = 1; bias / addend / residual and split-K as ever; no a2, out2, ln_out, GEGLU;
- *   tiles 2, 9, 11 (bf16) and 1, 2 (f32).
+ *   tiles with LDM_TILE_PHASE_BF16 / LDM_TILE_PHASE_F32 (ldm_gemm_tile_info).
  *   Cin must be a multiple of 128/sizeof(elem).
  *   Replaces: Conv2D 3x3 SAME (unet.py:22,40,71,375,378; autoencoder.py:32,35,
  *   148,275), pad(1,1)+stride-2 VALID (unet.py:26-27), ResizeNearestNeighbor+conv
@@ -123,7 +123,7 @@ typedef struct {
   int32_t dtype;         /* of a, w */
   int32_t out_dtype;     /* of out, residual */
   int32_t split_k;       /* 0 = let the library choose */
-  int32_t tile;          /* 0 = auto; 1-19 force an implicit-GEMM tile (9-12: bf16 16x16x32 MFMA path, 13-14: persistent ping-pong kernel; there split_k < 0 sets the workgroups per row panel, 15-16: tiles 9 / 11 with the halo-staged A operand for stride-1 convolutions whose 256-row M-tile is whole lines of one image, W = 16 or 32, 17-19: the 64x64 / 128x64 / 128x128 tiles with a 4- / 3- / 3-stage LDS ring for launches of 1-3 workgroups per CU), */
+  int32_t tile;          /* 0 = auto; 1 .. ldm_gemm_tile_count() - 1 force a tile: ldm_gemm_tile_info tells its shape, family and what it accepts (on a persistent tile split_k < 0 sets the workgroups per row panel) */
   float alpha;
   /* conv: 0 = one zero row/column before the image (Keras SAME at stride 1; pad (1,1)+VALID at
    * stride 2, unet.py:26-27); 1 = none before, one after -- the autoencoder's
@@ -156,7 +156,7 @@ typedef struct {
    *     LN(a) W^T + b  =  rstd_m * (sum_k a[m][k] w[n][k]  -  mean_m * ln_cs[n]) + bias[n],
    * and the kernel derives mean_m / rstd_m (eps = ln_eps, biased variance over the K columns) from
    * the A tiles it stages anyway: no LayerNorm launch, no normalised copy of the rows.  bf16 plain
-   * rows (conv = 0), batch 1, persistent tiles 13 / 14 (chosen automatically), epilogues: bias,
+   * rows (conv = 0), batch 1, persistent tiles (chosen automatically), epilogues: bias,
    * bias + GEGLU, or the transposed store (out2 with n_split = 0).  NULL = off. */
   const float* ln_cs;
   /* Split-K only: 1 = leave the float32 partial slabs in `workspace` and do NOT launch the reduce.  The
@@ -171,7 +171,7 @@ typedef struct {
    * a) read at the output pixel.  The ResidualBlock's shortcut (unet.py:379-380, :393-397: a Dense over the block
    * input where the channel count changes, added to the second convolution's output) then accumulates inside that
    * convolution's K loop: no launch and no [M][Cout] tensor of its own; pass bias = conv bias + shortcut bias.
-   * Cin2 a multiple of the K-tile (64 bf16 / 32 f32 elements); implicit-GEMM tiles 1-12 and 17-19 (not the
+   * Cin2 a multiple of the K-tile (64 bf16 / 32 f32 elements); LDM_TILE_A2 tiles (not the
    * persistent or halo-staged ones); split-K, deferred reduce and every epilogue as without it.  NULL = off. */
   const void* a2;
   int64_t lda2;
@@ -209,6 +209,28 @@ int ldm_gemm_ln_supported(int N, int dtype);
 /* the tile configuration and split-K factor ldm_gemm would pick for these params (host only;
  * nothing is launched) -- for tools and tests of the cost model */
 int ldm_gemm_plan(const ldm_gemm_params* p, int* tile, int* split_k);
+/* The tile table of ldm_gemm (host only): tiles 1 .. ldm_gemm_tile_count() - 1 exist (0 = auto). */
+#define LDM_TILE_PERSISTENT 1     /* persistent ping-pong kernel: bf16, N % bn == 0, no split-K */
+#define LDM_TILE_HALO 2           /* halo-staged A operand: bf16 stride-1 3x3 convolutions whose 256-row M-tile is whole
+                                     lines of one image, W = 16 or 32 */
+#define LDM_TILE_BF16_ONLY 4
+#define LDM_TILE_GEGLU 8          /* applies LDM_ACT_GEGLU ... */
+#define LDM_TILE_GEGLU_VEC 16     /* ... but unsplit only through the 16-byte vector epilogue */
+#define LDM_TILE_PHASE_F32 32     /* runs the phase form (upsample = 2) on float32 */
+#define LDM_TILE_PHASE_BF16 64    /* ... on bf16 */
+#define LDM_TILE_FORCED 128       /* the automatic plan never picks it: forced by the caller (plan tables) only */
+#define LDM_TILE_FORCED_BF16 256  /* the automatic plan picks it on float32 only */
+#define LDM_TILE_EXPERIMENTAL 512 /* not meant for plan tables either */
+#define LDM_TILE_A2 1024          /* takes a second A operand (a2) */
+#define LDM_TILE_WHOLE_N 2048     /* the automatic plan takes it only where N % bn == 0 (160/320-column tiles) */
+typedef struct {
+  int32_t bm, bn;        /* rows and columns of an output tile */
+  int32_t resident;      /* workgroups per CU */
+  uint32_t flags;        /* LDM_TILE_* */
+} ldm_gemm_tile;
+int ldm_gemm_tile_count(void);
+/* LDM_OK, or LDM_ERR_ARG for a tile outside 1 .. count - 1 */
+int ldm_gemm_tile_info(int tile, ldm_gemm_tile* out);
 /* bytes of workspace ldm_gemm may need for these params with split_k = 0 (auto) */
 size_t ldm_gemm_workspace_bytes(const ldm_gemm_params* p);
 

@@ -47,6 +47,15 @@ class GemmParams(C.Structure):
   ]
 
 
+class TileInfo(C.Structure):
+  """Mirror of `ldm_gemm_tile`; `flags` holds the LDM_TILE_* bits below."""
+  _fields_ = [("bm", c_i32), ("bn", c_i32), ("resident", c_i32), ("flags", c_u32)]
+
+
+(TILE_PERSISTENT, TILE_HALO, TILE_BF16_ONLY, TILE_GEGLU, TILE_GEGLU_VEC, TILE_PHASE_F32, TILE_PHASE_BF16, TILE_FORCED,
+ TILE_FORCED_BF16, TILE_EXPERIMENTAL, TILE_A2, TILE_WHOLE_N) = (1 << i for i in range(12))
+
+
 # name -> (restype, argtypes); must list EVERY function of include/ldm_hip.h
 SIGNATURES = {
     "ldm_version": (c_i32, []),
@@ -136,6 +145,8 @@ SIGNATURES = {
                                     c_i32, c_i32, c_vp]),
     "ldm_gemm_plan": (c_i32, [c_vp, c_vp, c_vp]),
     "ldm_gemm_ln_supported": (c_i32, [c_i32, c_i32]),
+    "ldm_gemm_tile_count": (c_i32, []),
+    "ldm_gemm_tile_info": (c_i32, [c_i32, C.POINTER(TileInfo)]),
     "ldm_gaussian_sample": (c_i32, [c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_vp]),
     "ldm_vq_nearest": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp]),
     "ldm_embedding": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
@@ -165,6 +176,16 @@ def _load():
 
 
 lib = _load()
+
+
+def tile_table():
+  """{tile: (bm, bn, resident workgroups per CU, TILE_* flags)}: ldm_gemm's tile table, read through ldm_gemm_tile_info."""
+  info, out = TileInfo(), {}
+  for t in range(1, lib.ldm_gemm_tile_count()):
+    if lib.ldm_gemm_tile_info(t, C.byref(info)) != OK:
+      raise ImportError(f"ldm_gemm_tile_info({t}) failed")
+    out[t] = (info.bm, info.bn, info.resident, info.flags)
+  return out
 
 
 def last_error() -> str:

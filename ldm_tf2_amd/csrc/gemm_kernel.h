@@ -44,8 +44,6 @@ struct GemmArgs {
   int phase_adjacent;        // MODE 4: tile order (0 = phase-major, 1 = the four phases of an M-tile adjacent)
 };
 
-constexpr int kLnTile = 8;   // the tile whose BN (320) holds a whole row of the N = 320 layers
-
 constexpr uint32_t kOOB = 0x80000000u;   // >= any num_records we accept: load returns 0
 
 __device__ __forceinline__ void mma32(f32x16& acc, const u32x4& a, const u32x4& b, bf16_t) {
@@ -899,8 +897,5 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(GemmArgs p) {
 // host-side launcher of one (element type, MODE) pair; defined in gemm_inst_*.hip
 template <typename T, int MODE>
 void launch_cfg(int cfg, const GemmArgs& a, dim3 grid, hipStream_t s);
-// launcher of the MODE 4 tiles (the phase form of the upsample convolution); defined in gemm_inst_up2.hip
-template <typename T>
-void launch_phase(int cfg, const GemmArgs& a, dim3 grid, hipStream_t s);
 
 }  // namespace ldm_gemm_detail

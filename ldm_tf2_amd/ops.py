@@ -147,15 +147,16 @@ def _active():
 
 def _active_cfg():
   return getattr(_TLS, "active_cfg", None)
-_TILE_DIMS = {1: (256, 128, 1), 2: (128, 128, 2), 3: (128, 64, 3), 4: (64, 64, 5), 6: (128, 160, 2),
-              7: (256, 160, 1), 8: (128, 320, 1),       # BM, BN, resident workgroups per CU
-              9: (256, 160, 1), 10: (128, 160, 2), 11: (256, 128, 1), 12: (128, 128, 2),   # bf16 16x16x32 MFMA path
-              13: (256, 160, 1), 14: (256, 128, 1),     # persistent ping-pong kernel (no split-K, N % BN == 0)
-              15: (256, 160, 1), 16: (256, 128, 1),     # tiles 9 / 11 with the halo-staged A operand (stride-1 convs)
-              17: (64, 64, 2), 18: (128, 64, 2), 19: (128, 128, 1)}   # tiles 4 / 3 / 2 with a 4- / 3- / 3-stage LDS ring
-_BF16_TILES = (9, 10, 11, 12, 13, 14, 15, 16)
-_PERSISTENT_TILES = (13, 14)
-_HALO_RING_TILES = (15, 16)
+
+
+_TILES = _lib.tile_table()      # {tile: (BM, BN, resident workgroups per CU, LDM_TILE_* flags)}, csrc/gemm_tiles.h
+_tiles_with = lambda flag: tuple(t for t, row in _TILES.items() if row[3] & flag)
+_TILE_DIMS = {t: row[:3] for t, row in _TILES.items() if not row[3] & _lib.TILE_EXPERIMENTAL}   # what a plan may name
+_BF16_TILES = _tiles_with(_lib.TILE_BF16_ONLY)
+_PERSISTENT_TILES = _tiles_with(_lib.TILE_PERSISTENT)   # no split-K, N % BN == 0
+_HALO_RING_TILES = _tiles_with(_lib.TILE_HALO)          # stride-1 convs whose M-tile is whole lines of one image
+_GEGLU_TILES = _tiles_with(_lib.TILE_GEGLU)
+_WHOLE_N_TILES = _tiles_with(_lib.TILE_WHOLE_N)         # offered only where N % BN == 0 (the N = 160*k layers)
 
 
 def _halo_ring_key(key, M, N, bn):
@@ -278,13 +279,9 @@ def plan_candidates(M, N, K, batch, act, dtype, key=None):
   ktiles = K // (64 if dtype == BF16 else 32)
   out = []
   for tile, (bm, bn, res) in _TILE_DIMS.items():
-    if tile in _HALO_RING_TILES and not (dtype == BF16 and batch == 1 and _halo_ring_key(key, M, N, bn)):
-      continue
-    if act == ACT_GEGLU and tile not in (1, 2, 11, 12, 14, 19):
-      continue
-    if tile in _BF16_TILES and dtype != BF16:
-      continue
-    if bn % 160 == 0 and N % bn != 0:
+    if ((tile in _HALO_RING_TILES and not (dtype == BF16 and batch == 1 and _halo_ring_key(key, M, N, bn))) or
+        (act == ACT_GEGLU and tile not in _GEGLU_TILES) or (tile in _BF16_TILES and dtype != BF16) or
+        (tile in _WHOLE_N_TILES and N % bn != 0)):
       continue
     tiles = -(-M // bm) * -(-N // bn) * batch
     if tile in _PERSISTENT_TILES:
@@ -323,7 +320,7 @@ def resolve_plan(p: GemmParams):
     plan = active.get(key)
     if plan is None and p.ln_cs:
       # a LayerNorm-fold launch without an entry of its own inherits the plain product's plan when
-      # that names a persistent tile (13 = 160-column, 14 = 128-column n-tiles)
+      # that names a persistent tile
       plan = active.get(key[:-len(" ln1")])
       if plan is not None and plan[0] not in _PERSISTENT_TILES:
         plan = None
@@ -358,58 +355,70 @@ def finish(pending):
   _outstanding().pop(pending.ws.data_ptr(), None)
 
 
-def _gemm_deferred(p: GemmParams, device, out, keep):
-  """ldm_gemm with the reduce left to the caller.  Returns a PendingReduce, or None when the plan does
-  not split K (the product is then complete)."""
+def _launch(p: GemmParams, device, defer=None):
+  """The one ldm_gemm launch sequence: this thread's workspace, the plan table's (tile, split) if it has one, the
+  launch.  With `defer` = (out, keep) a split-K plan leaves its slabs in the workspace: returns its PendingReduce."""
   ws = workspace(device)
   if ws.data_ptr() in _outstanding():
-    raise RuntimeError("ldm_gemm: this workspace still holds the slabs of a deferred split-K product")
-  p.workspace = ws.data_ptr()
-  p.workspace_bytes = ws.numel()
+    raise RuntimeError("ldm_gemm: this workspace still holds the slabs of a deferred split-K product "
+                       "(ops.finish it, or let the GroupNorm that follows consume it, first)")
+  p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
   planned = resolve_plan(p)
   while True:
-    split = lib.ldm_gemm_splits(C.byref(p)) > 1
-    p.defer_reduce = 1 if split else 0
+    split = defer is not None and lib.ldm_gemm_splits(C.byref(p)) > 1
+    p.defer_reduce = int(split)
     st = lib.ldm_gemm(C.byref(p), _stream())
     if st in (_lib.ERR_ARG, _lib.ERR_WORKSPACE) and planned:
-      # the table's tile cannot run THIS launch (a plan key names the shape, not the epilogue; see _gemm): once
-      # more on the cost model, without consulting the table again.  Nothing was enqueued by the rejected call.
-      planned = False
-      p.tile, p.split_k = 0, 0
+      # A plan key names the shape, not the epilogue: the table's persistent / halo tile exists only for the epilogue
+      # variants that are instantiated.  A launch that shares a key with a tuned one but not its epilogue runs once
+      # more, on the cost model.  Nothing was enqueued by the rejected call (argument checks precede every launch).
+      planned, p.tile, p.split_k = False, 0, 0
       continue
     check(st, "ldm_gemm")
-    break
-  if not split:
+    if split:
+      _outstanding()[ws.data_ptr()] = pend = PendingReduce(p, defer[0], ws, defer[1])
+      return pend
     return None
-  pend = PendingReduce(p, out, ws, keep)
-  _outstanding()[ws.data_ptr()] = pend
-  return pend
+
+
+def _gemm_deferred(p: GemmParams, device, out, keep):
+  """ldm_gemm with the reduce left to the caller: a PendingReduce, or None when the plan does not split K."""
+  return _launch(p, device, (out, keep))
 
 
 def _gemm(p: GemmParams, device):
   """Every ldm_gemm launch of the package goes through here (tools/gemm_hooks.py wraps this
   one function for measurements; the product path itself carries no hooks)."""
-  ws = workspace(device)
-  if ws.data_ptr() in _outstanding():
-    raise RuntimeError("ldm_gemm: this workspace still holds the slabs of a deferred split-K product "
-                       "(ops.finish it, or let the GroupNorm that follows consume it, first)")
-  p.workspace = ws.data_ptr()
-  p.workspace_bytes = ws.numel()
-  planned = resolve_plan(p)
-  st = lib.ldm_gemm(C.byref(p), _stream())
-  if st in (_lib.ERR_ARG, _lib.ERR_WORKSPACE) and planned:
-    # A plan key names the shape, not the epilogue: the table's persistent / halo tile exists only for
-    # the epilogue variants that are instantiated.  A launch that shares a key with a tuned one but not
-    # its epilogue (another U-Net configuration) runs on the cost model instead of failing.  Nothing
-    # was enqueued by the rejected call (argument checks precede every launch).
-    p.tile, p.split_k = 0, 0
-    st = lib.ldm_gemm(C.byref(p), _stream())
-  check(st, "ldm_gemm")
+  _launch(p, device)
 
 
 def linear_ln_supported(n_out, dtype):
   """True if `linear(..., ln=...)` can emit the LayerNorm of its output rows in the same launch."""
   return bool(lib.ldm_gemm_ln_supported(int(n_out), code(dtype)))
+
+
+def _row_params(x, wt, out, M, N, K, bias=None, addend=None, add_rows=0, residual=None, x2=None, act=ACT_NONE,
+                alpha=1.0, tile=0, split_k=0):
+  """GemmParams of a batch-1 product with a row-major output; `x2` [M rows] holds the last columns of K (ldm_gemm a2)."""
+  p = GemmParams()
+  p.a, p.w, p.out = _ptr(x), _ptr(wt), _ptr(out)
+  p.bias = _ptr(_f32(bias, "bias"))
+  p.addend = _ptr(_f32(addend, "addend"))
+  p.residual = _ptr(residual)
+  if residual is not None:
+    assert residual.dtype == out.dtype
+    p.ldr = row_ld(residual)
+  p.lda, p.ldc_m, p.ldc_n = row_ld(x), row_ld(out), 1
+  p.M, p.N, p.K, p.batch = M, N, K, 1
+  if x2 is not None:
+    assert x2.dtype == x.dtype and x2.numel() // x2.shape[-1] == M
+    p.a2, p.lda2, p.Cin2 = _ptr(x2), row_ld(x2), x2.shape[-1]
+  if addend is not None:
+    p.add_rows = add_rows
+    p.add_ld = addend.stride(0) if (addend.dim() == 2 and addend.shape[0] > 1) else 0
+  p.act, p.dtype, p.out_dtype, p.alpha = act, code(x.dtype), code(out.dtype), alpha
+  p.tile, p.split_k = tile, split_k
+  return p
 
 
 def linear(x, wt, out, bias=None, act=ACT_NONE, residual=None, addend=None, add_rows=0,
@@ -425,30 +434,10 @@ def linear(x, wt, out, bias=None, act=ACT_NONE, residual=None, addend=None, add_
   `ln_fold=(cs, eps)`: out = LayerNorm(x) . W^T + b with the normalisation folded into the product:
   `wt` holds gamma (.) W, `bias` holds b + W beta, cs[n] = sum_k wt[n, k] (layout.ln_fold); the kernel
   derives the row statistics itself (bf16, persistent tiles)."""
-  K1 = x.shape[-1]
-  K2 = 0 if x2 is None else x2.shape[-1]
-  K = K1 + K2
-  N = wt.shape[0]
-  M = x.numel() // K1
+  K1, K2 = x.shape[-1], (0 if x2 is None else x2.shape[-1])
+  K, N, M = K1 + K2, wt.shape[0], x.numel() // K1
   assert wt.shape[1] == K and wt.is_contiguous() and wt.dtype == x.dtype
-  p = GemmParams()
-  p.a, p.w, p.out = _ptr(x), _ptr(wt), _ptr(out)
-  p.bias = _ptr(_f32(bias, "bias"))
-  p.addend = _ptr(_f32(addend, "addend"))
-  p.residual = _ptr(residual)
-  if residual is not None:
-    assert residual.dtype == out.dtype
-    p.ldr = row_ld(residual)
-  p.lda, p.ldc_m, p.ldc_n = row_ld(x), row_ld(out), 1
-  p.M, p.N, p.K, p.batch = M, N, K, 1
-  if x2 is not None:     # the last K2 columns of K multiply rows of a second matrix (ldm_gemm a2)
-    assert x2.numel() // K2 == M and x2.dtype == x.dtype
-    p.a2, p.lda2, p.Cin2 = _ptr(x2), row_ld(x2), K2
-  if addend is not None:
-    p.add_rows = add_rows if add_rows > 0 else M
-    p.add_ld = addend.stride(0) if (addend.dim() == 2 and addend.shape[0] > 1) else 0
-  p.act, p.dtype, p.out_dtype, p.alpha = act, code(x.dtype), code(out.dtype), alpha
-  p.tile, p.split_k = tile, split_k
+  p = _row_params(x, wt, out, M, N, K, bias, addend, add_rows if add_rows > 0 else M, residual, x2, act, alpha, tile, split_k)
   if out2 is not None:
     assert out2.dtype == out.dtype and out2.dim() == 3 and out2.stride(2) == 1 and M % out2.shape[0] == 0
     assert out.shape[-1] + out2.shape[1] == N and out2.shape[2] >= M // out2.shape[0]
@@ -484,12 +473,10 @@ def linear_t_supported(x, wt, out_t):
 def linear_t(x, wt, out_t, tile=0, bias=None, ln_fold=None):
   """out_t[g, n, t] = sum_k x[g * T + t, k] * wt[n, k] with T = M / G: the product stored
   TRANSPOSED per group of T rows (the self-attention V projection lands directly in the attention
-  kernel's V^T [rows, heads*Sp, T]).  Runs on the persistent kernel (tile 13 / 14; the plan table
+  kernel's V^T [rows, heads*Sp, T]).  Runs on the persistent kernel (_PERSISTENT_TILES; the plan table
   may name which)."""
-  K = x.shape[-1]
-  N = wt.shape[0]
+  K, N, G = x.shape[-1], wt.shape[0], out_t.shape[0]
   M = x.numel() // K
-  G = out_t.shape[0]
   assert wt.shape[1] == K and wt.is_contiguous() and wt.dtype == x.dtype
   assert out_t.dim() == 3 and out_t.shape[1] == N and out_t.shape[2] >= M // G
   p = GemmParams()
@@ -507,7 +494,8 @@ def linear_t(x, wt, out_t, tile=0, bias=None, ln_fold=None):
     p.ln_cs, p.ln_eps = _ptr(_f32(cs, "ln_fold column sums")), float(eps)
   resolve_plan(p)
   if p.tile not in _PERSISTENT_TILES:
-    p.tile, p.split_k = (14 if N % 128 == 0 else 13), 0
+    by_bn = sorted(_PERSISTENT_TILES, key=lambda t: _TILE_DIMS[t][1])   # the narrowest n-tiles that divide N, else the widest
+    p.tile, p.split_k = next((t for t in by_bn if N % _TILE_DIMS[t][1] == 0), by_bn[-1]), 0
   _gemm(p, x.device)
   return out_t
 
@@ -521,26 +509,10 @@ def _conv_params(x, wt, out, bias, stride, upsample, addend, residual, tile, spl
   Cin2 = 0 if x2 is None else x2.shape[-1]
   assert wt.shape[1] == 9 * Cin + Cin2 and wt.is_contiguous() and wt.dtype == x.dtype
   assert tuple(out.shape) == (B, OH, OW, Cout), (tuple(out.shape), (B, OH, OW, Cout))
-  p = GemmParams()
-  p.a, p.w, p.out = _ptr(x), _ptr(wt), _ptr(out)
-  p.bias = _ptr(_f32(bias, "bias"))
-  p.addend = _ptr(_f32(addend, "addend"))
-  p.residual = _ptr(residual)
-  if residual is not None:
-    assert residual.dtype == out.dtype
-    p.ldr = row_ld(residual)
-  p.lda, p.ldc_m, p.ldc_n = row_ld(x), row_ld(out), 1
-  p.M, p.N, p.K, p.batch = B * OH * OW, Cout, 9 * Cin + Cin2, 1
-  if x2 is not None:
-    assert tuple(x2.shape[:3]) == (B, OH, OW) and x2.dtype == x.dtype and stride == 1 and not upsample
-    p.a2, p.lda2, p.Cin2 = _ptr(x2), row_ld(x2), Cin2
-  if addend is not None:
-    p.add_rows = OH * OW
-    p.add_ld = addend.stride(0) if (addend.dim() == 2 and addend.shape[0] > 1) else 0
+  assert x2 is None or (tuple(x2.shape[:3]) == (B, OH, OW) and stride == 1 and not upsample)
+  p = _row_params(x, wt, out, B * OH * OW, Cout, 9 * Cin + Cin2, bias, addend, OH * OW, residual, x2, tile=tile, split_k=split_k)
   p.conv, p.B, p.H, p.W, p.Cin, p.OH, p.OW = 1, B, H, W, Cin, OH, OW
   p.stride, p.upsample, p.no_lead_pad = stride, int(bool(upsample)), int(bool(no_lead_pad))
-  p.act, p.dtype, p.out_dtype, p.alpha = ACT_NONE, code(x.dtype), code(out.dtype), 1.0
-  p.tile, p.split_k = tile, split_k
   return p
 
 
@@ -565,15 +537,9 @@ def _up2_params(x, wt4, out, bias, tile, split_k):
   assert wt4.dim() == 3 and wt4.shape[0] == 4 and wt4.is_contiguous() and wt4.dtype == x.dtype
   Cout = wt4.shape[1]
   assert tuple(out.shape) == (B, 2 * H, 2 * W, Cout), (tuple(out.shape), (B, 2 * H, 2 * W, Cout))
-  p = GemmParams()
-  p.a, p.w, p.out = _ptr(x), _ptr(wt4), _ptr(out)
-  p.bias = _ptr(_f32(bias, "bias"))
-  p.lda, p.ldc_m, p.ldc_n = row_ld(x), row_ld(out), 1
-  p.M, p.N, p.K, p.batch = B * 4 * H * W, Cout, wt4.shape[2], 1
+  p = _row_params(x, wt4, out, B * 4 * H * W, Cout, wt4.shape[2], bias, tile=tile, split_k=split_k)
   p.conv, p.B, p.H, p.W, p.Cin, p.OH, p.OW = 1, B, H, W, Cin, 2 * H, 2 * W
   p.stride, p.upsample, p.no_lead_pad = 1, 2, 0
-  p.act, p.dtype, p.out_dtype, p.alpha = ACT_NONE, code(x.dtype), code(out.dtype), 1.0
-  p.tile, p.split_k = tile, split_k
   return p
 
 

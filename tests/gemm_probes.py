@@ -87,8 +87,8 @@ import torch
 F32, BF, F64, I64 = torch.float32, torch.bfloat16, torch.float64, torch.int64
 MAX_PHASES = 4
 
-# ---- the tile table: bm, bn, LDS ring depth, bf16 only (gemm.hip kTiles / kBf16Only, gemm_kernel.h NSTAGE; the tests
-# cross-check bm / bn with ops._TILE_DIMS, the csrc text and ldm_gemm's own rejections) -----------------------------
+# ---- the tile table: bm, bn, LDS ring depth, bf16 only (gemm_tiles.h kTiles, gemm_kernel.h NSTAGE; the tests
+# cross-check bm / bn with ops._TILE_DIMS, ldm_gemm_tile_info and ldm_gemm's own rejections) -----------------------
 Tile = namedtuple("Tile", "bm bn stages bf16_only")
 TILES = {1: Tile(256, 128, 3, False), 2: Tile(128, 128, 2, False), 3: Tile(128, 64, 2, False), 4: Tile(64, 64, 2, False),
          5: Tile(256, 128, 2, False), 6: Tile(128, 160, 2, False), 7: Tile(256, 160, 3, False), 8: Tile(128, 320, 2, False),

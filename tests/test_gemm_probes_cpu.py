@@ -1,7 +1,7 @@
 """The GEMM / convolution probes (tests/gemm_probes.py) are as sharp as claimed: shown on the reference alone, without a
 GPU, for every case of the matrix test_gemm_accounting_gpu.py runs.
 
-* the tile table agrees with kTiles in csrc/gemm.hip, with ops._TILE_DIMS and with the plan ldm_gemm makes (host query);
+* the tile table agrees with the library's own (ldm_gemm_tile_info), with ops._TILE_DIMS and with the plan ldm_gemm makes;
 * the matrix holds, per form, every M, N and K-tile edge value relative to that form's bm, bn and ring depth, every
   image geometry and convolution form, the layouts and the split-K shapes;
 * per case: every stored value is exactly representable (|ref| <= 256 where the output is bf16), every partial sum is
@@ -11,8 +11,6 @@ GPU, for every case of the matrix test_gemm_accounting_gpu.py runs.
 * the reference equals oracle.ldm_oracle.conv2d / upsample_nearest2x / a float64 matmul once per mode.
 """
 import ctypes as C
-import os
-import re
 
 import pytest
 import torch
@@ -21,26 +19,33 @@ import gemm_probes as G
 
 CASES = G.all_cases()
 BY_FORM = {name: [c for c in CASES if c.form == name] for name in G.FORMS}
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_tile_table_matches_the_sources():
-  src = open(os.path.join(ROOT, "ldm_tf2_amd", "csrc", "gemm.hip")).read()
-  body = src[src.index("kTiles[kNumTiles] = {"):src.index("constexpr int kResident")]
-  body = re.sub(r"//[^\n]*", "", body)
-  pairs = [(int(a), int(b)) for a, b in re.findall(r"\{(\d+),\s*(\d+)\}", body)]
-  assert len(pairs) == 20 and pairs[0] == (0, 0)
+  from ldm_tf2_amd import _lib as L, ops
+  lib, info, rows = L.lib, L.TileInfo(), {}
+  assert lib.ldm_gemm_tile_count() == 20
+  for t in (0, 20, -1):
+    assert lib.ldm_gemm_tile_info(t, C.byref(info)) == L.ERR_ARG
+  for t in range(1, 20):
+    assert lib.ldm_gemm_tile_info(t, C.byref(info)) == 0
+    rows[t] = (info.bm, info.bn, info.resident, info.flags)
   for t, tile in G.TILES.items():
-    assert pairs[t] == (tile.bm, tile.bn), t
-  bf = re.search(r"kBf16Only\[kNumTiles\] = \{([^}]*)\}", src).group(1).split(",")
-  assert [s.strip() == "true" for s in bf][1:] == [G.TILES[t].bf16_only for t in range(1, 20)]
-  from ldm_tf2_amd import ops
-  for t, (bm, bn, _) in ops._TILE_DIMS.items():
-    assert (G.TILES[t].bm, G.TILES[t].bn) == (bm, bn), t
+    assert rows[t][:2] == (tile.bm, tile.bn), t
+    assert bool(rows[t][3] & L.TILE_BF16_ONLY) == tile.bf16_only, t
+  with_flag = lambda f: {t for t, r in rows.items() if r[3] & f}
+  assert with_flag(L.TILE_PERSISTENT) == set(G.PERSISTENT) and with_flag(L.TILE_HALO) == set(G.HALO)
+  # resident workgroups per CU: what the LDS ring (stages x (bm + bn) x 128 bytes, + 2 halo patches) leaves of 160 KiB,
+  # as the cost model counts them; GEGLU: the tiles whose width is a multiple of 64 and whose epilogue pairs value / gate
+  assert [rows[t][2] for t in range(1, 20)] == [1, 2, 3, 5, 1, 2, 1, 1, 1, 2, 1, 2, 1, 1, 1, 1, 2, 2, 1]
+  assert with_flag(L.TILE_GEGLU) == {1, 2, 5, 11, 12, 14, 19} and with_flag(L.TILE_GEGLU_VEC) == {11, 12}
+  assert all(G.TILES[t].bn % 64 == 0 for t in with_flag(L.TILE_GEGLU))
+  assert ops._TILE_DIMS == {t: r[:3] for t, r in rows.items() if t != 5}
+  assert ops._BF16_TILES == tuple(t for t in range(1, 20) if G.TILES[t].bf16_only)
   assert set(ops._PERSISTENT_TILES) == set(G.PERSISTENT) and set(ops._HALO_RING_TILES) == set(G.HALO)
   # ring depths: gemm_kernel.h NSTAGE = NS, else 3 for the halo ring, else 3 where two stages already fill a CU's LDS for
   # one 8-wave workgroup and three still fit, else 2; the persistent kernel: 3 (gemm3_kernel.h)
-  waves8 = {1, 7, 8, 9, 11}                                       # gemm_launch.h: the 512-thread forms
+  waves8 = {1, 7, 8, 9, 11}                                       # gemm_tiles.h: the 8-wave (wm x wn) forms
   for t, tile in G.TILES.items():
     stage = (tile.bm + tile.bn) * 128
     want = {17: 4, 18: 3, 19: 3}.get(t, 3 if t in G.PERSISTENT + G.HALO else
