@@ -112,6 +112,25 @@ class _Blocks:
     ops.linear(o, a.o[0], out, bias=a.o[1], residual=x)
     return out
 
+  _taps = None
+
+  def _tap(self, name, t):
+    """decode / encode (taps=): a clone of stage output `t` under its weight prefix (no product is deferred here)."""
+    if self._taps is not None:
+      self._taps[name] = t.clone()
+    return t
+
+  def _tap_scope(self, taps, chunks, what):
+    if taps is None:
+      return None
+    if not isinstance(taps, dict):
+      raise ValueError(f"{what}(taps=) takes a dict")
+    if chunks != 1:
+      raise ValueError(f"{what}(taps=) needs a batch that runs as one chunk, this one takes {chunks}")
+    if torch.cuda.is_current_stream_capturing():
+      raise ValueError(f"{what}(taps=) is eager only: a capturing stream cannot hand out clones")
+    return taps
+
   def _dst(self, cur, shape):
     """Ping-pong activation buffer of `shape` that is not `cur`."""
     t = self.buf.get("act_a", shape, self.dtype)
@@ -153,22 +172,28 @@ class _Decoder(_Blocks):
     self._ws = ops.new_workspace(dev)
     self.max_chunk = 16
 
-  def decode(self, latents, scale_factor=1.0, force_quantize=False):
+  def decode(self, latents, scale_factor=1.0, force_quantize=False, taps=None):
     """latents f32 [B,h,w,C]; computes Decoder(post_quant(quantize?(latents / scale_factor))).
     Large batches run in chunks (samples are independent): no kernel operand may reach 2 GiB
     (ldm_gemm addresses operands with 32-bit buffer offsets) and the scratch stays bounded
     (`max_chunk` images at a time); the last chunk is the window ending at B, so every chunk
-    has the same shape and reuses the same scratch buffers."""
+    has the same shape and reuses the same scratch buffers.
+    `taps` (a dict; eager only, one chunk): a clone of every stage's output in the storage type -- conv_in,
+    middle/residual1 | attention | residual2, up/{i}, out; the launches are those of the call without it."""
     assert latents.dtype == torch.float32 and latents.is_contiguous()
     B, h, w, c = latents.shape
     f = 2 ** sum(1 for blk in self.up if blk[0] == "up")
     cout = self.conv_out[0].shape[-1]
     out = torch.empty(B, f * h, f * w, cout, dtype=torch.float32, device=self.device)
     n = _chunk_rows(B, self._max_sample_elems(h, w), self.dtype, self.max_chunk)
-    with ops.workspace_scope(self._ws):
-      for i in range(0, B, n):
-        i0 = min(i, B - n)
-        self._decode_chunk(latents[i0:i0 + n], scale_factor, force_quantize, out[i0:i0 + n])
+    self._taps = self._tap_scope(taps, -(-B // n), "decode")
+    try:
+      with ops.workspace_scope(self._ws):
+        for i in range(0, B, n):
+          i0 = min(i, B - n)
+          self._decode_chunk(latents[i0:i0 + n], scale_factor, force_quantize, out[i0:i0 + n])
+    finally:
+      self._taps = None
     return out
 
   def _max_sample_elems(self, h, w):
@@ -209,10 +234,11 @@ class _Decoder(_Blocks):
     ch = self.mid[0].cin
     cur = self._dst(None, (B, h, w, ch))
     ops.conv3x3_small(x0, self.conv_in[0], self.conv_in[1], cur)
-    cur = self._res(self.mid[0], cur, self._dst(cur, (B, h, w, ch)))
-    cur = self._attn(self.mid[1], cur, self._dst(cur, (B, h, w, ch)))   # always (autoencoder.py:193)
-    cur = self._res(self.mid[2], cur, self._dst(cur, (B, h, w, ch)))
-    for blk in self.up:
+    self._tap("conv_in", cur)
+    cur = self._tap("middle/residual1", self._res(self.mid[0], cur, self._dst(cur, (B, h, w, ch))))
+    cur = self._tap("middle/attention", self._attn(self.mid[1], cur, self._dst(cur, (B, h, w, ch))))   # always (autoencoder.py:193)
+    cur = self._tap("middle/residual2", self._res(self.mid[2], cur, self._dst(cur, (B, h, w, ch))))
+    for i, blk in enumerate(self.up):
       hh, ww = cur.shape[1], cur.shape[2]
       if blk[0] == "up":
         dst = self._dst(cur, (B, 2 * hh, 2 * ww, blk[1].shape[-2]))        # autoencoder.py:152-155
@@ -225,10 +251,11 @@ class _Decoder(_Blocks):
         cur = self._res(r, cur, self._dst(cur, (B, hh, ww, r.cout)))
         if a is not None and hh in self.attention_resolutions:            # autoencoder.py:176
           cur = self._attn(a, cur, self._dst(cur, (B, hh, ww, r.cout)))
+      self._tap(f"up/{i}", cur)
     t0 = B_.get("gn", tuple(cur.shape), dt)
     ops.groupnorm(cur, self.gn_out[0], self.gn_out[1], t0, GROUP_NORM_EPS, silu=True, partial=self._gnp)
     ops.conv3x3_small(t0, self.conv_out[0], self.conv_out[1], out)
-    return out
+    return self._tap("out", out)
 
 
 class _Encoder(_Blocks):
@@ -260,11 +287,12 @@ class _Encoder(_Blocks):
     self._ws = ops.new_workspace(dev)
     self.max_chunk = 16
 
-  def encode(self, images, max_chunk=None):
+  def encode(self, images, max_chunk=None, taps=None):
     """images f32 [B,H,W,3] -> quant_conv(Encoder(images)) f32 [B,H/f,W/f,zc]; chunked over the
     batch like `_Decoder.decode`.  `max_chunk` (default: the encoder's own) bounds the images per pass;
     1 = every image on its own, so its latents do not depend on the batch it arrived in (the launch
-    plans of a pass depend on its row count)."""
+    plans of a pass depend on its row count).  `taps` (a dict; eager only, one chunk): a clone of every stage's
+    output in the storage type -- conv_in, down/{i}, middle/residual1 | attention | residual2, out."""
     assert images.dtype == torch.float32 and images.is_contiguous()
     B, H, W, _ = images.shape
     f = 2 ** sum(1 for blk in self.down if blk[0] == "down")
@@ -276,10 +304,14 @@ class _Encoder(_Blocks):
       else:
         per = max(per, hh * ww * max(blk[1].cin, blk[1].cout))
     n = _chunk_rows(B, per, self.dtype, max_chunk or self.max_chunk)
-    with ops.workspace_scope(self._ws):
-      for i in range(0, B, n):
-        i0 = min(i, B - n)
-        self._encode_chunk(images[i0:i0 + n], out[i0:i0 + n])
+    self._taps = self._tap_scope(taps, -(-B // n), "encode")
+    try:
+      with ops.workspace_scope(self._ws):
+        for i in range(0, B, n):
+          i0 = min(i, B - n)
+          self._encode_chunk(images[i0:i0 + n], out[i0:i0 + n])
+    finally:
+      self._taps = None
     return out
 
   def _encode_chunk(self, images, out):
@@ -289,7 +321,8 @@ class _Encoder(_Blocks):
     ch = self.conv_in[0].shape[-1]
     cur = self._dst(None, (B, H, W, ch))
     ops.conv3x3_small(images, self.conv_in[0], self.conv_in[1], cur)
-    for blk in self.down:
+    self._tap("conv_in", cur)
+    for i, blk in enumerate(self.down):
       hh, ww = cur.shape[1], cur.shape[2]
       if blk[0] == "down":                                               # autoencoder.py:133-136
         dst = self._dst(cur, (B, hh // 2, ww // 2, blk[1].shape[0]))
@@ -299,16 +332,17 @@ class _Encoder(_Blocks):
         cur = self._res(r, cur, self._dst(cur, (B, hh, ww, r.cout)))
         if a is not None and hh in self.attention_resolutions:            # autoencoder.py:117
           cur = self._attn(a, cur, self._dst(cur, (B, hh, ww, r.cout)))
+      self._tap(f"down/{i}", cur)
     shp = tuple(cur.shape)
-    cur = self._res(self.mid[0], cur, self._dst(cur, shp))
-    cur = self._attn(self.mid[1], cur, self._dst(cur, shp))
-    cur = self._res(self.mid[2], cur, self._dst(cur, shp))
+    cur = self._tap("middle/residual1", self._res(self.mid[0], cur, self._dst(cur, shp)))
+    cur = self._tap("middle/attention", self._attn(self.mid[1], cur, self._dst(cur, shp)))
+    cur = self._tap("middle/residual2", self._res(self.mid[2], cur, self._dst(cur, shp)))
     t0 = B_.get("gn", shp, dt)
     ops.groupnorm(cur, self.gn_out[0], self.gn_out[1], t0, GROUP_NORM_EPS, silu=True, partial=self._gnp)
     h = B_.get("enc_h", (B, shp[1], shp[2], self.zc), torch.float32)
     ops.conv3x3(t0, self.conv_out[0], h, bias=self.conv_out[1])
     ops.post_quant(h, 1.0, self.quant[0], self.quant[1], out)
-    return out
+    return self._tap("out", out)
 
 
 class DiagonalGaussian:
@@ -356,12 +390,12 @@ class _AutoencoderBase:
     self._decoder = _Decoder(weights, dtype, self.device, attention_resolutions, phase_upsample=phase_upsample)
     self._encoder = _Encoder(weights, dtype, self.device, attention_resolutions) if with_encoder else None
 
-  def _encode(self, inputs, per_sample=False):
+  def _encode(self, inputs, per_sample=False, taps=None):
     if self._encoder is None:
       raise RuntimeError("this autoencoder was built without its encoder: pass with_encoder=True "
                          "(or weights that contain encoder/*)")
     x = torch.as_tensor(inputs, dtype=torch.float32).to(self.device).contiguous()
-    return self._encoder.encode(x, max_chunk=1 if per_sample else None)
+    return self._encoder.encode(x, max_chunk=1 if per_sample else None, taps=taps)
 
 
 class AutoencoderKL(_AutoencoderBase):
@@ -383,15 +417,15 @@ class AutoencoderKL(_AutoencoderBase):
                      multipliers=self._multipliers, attention_resolutions=(), image_size=image_size,
                      double_z=True), phase_upsample=phase_upsample)
 
-  def encode(self, inputs, training=False, per_sample=False):
+  def encode(self, inputs, training=False, per_sample=False, taps=None):
     """autoencoder.py:353-359: images [B,H,W,3] -> DiagonalGaussian posterior.  `per_sample`: one encoder pass
     per image, so an image's moments are the same bits in any batch."""
-    return DiagonalGaussian(self._encode(inputs, per_sample))
+    return DiagonalGaussian(self._encode(inputs, per_sample, taps))
 
-  def decode(self, inputs, training=False, scale_factor=1.0):
+  def decode(self, inputs, training=False, scale_factor=1.0, taps=None):
     """autoencoder.py:361-364."""
     x = torch.as_tensor(inputs, dtype=torch.float32).to(self.device).contiguous()
-    return self._decoder.decode(x, scale_factor=scale_factor)
+    return self._decoder.decode(x, scale_factor=scale_factor, taps=taps)
 
   def call(self, inputs, sample_posterior=True, training=False, noise=None, seed=0):
     """autoencoder.py:344-351: (decode(posterior.sample() | posterior.mode()), posterior).  The
@@ -429,10 +463,10 @@ class AutoencoderVQ(_AutoencoderBase):
                      image_size=image_size or latent_size * 2 ** (len(self._multipliers) - 1),
                      double_z=False))
 
-  def encode(self, inputs, only_encode=False, training=False, per_sample=False):
+  def encode(self, inputs, only_encode=False, training=False, per_sample=False, taps=None):
     """autoencoder.py:411-419: latents, or (quantized latents, codebook_loss, indices).  `per_sample` as in
     AutoencoderKL.encode."""
-    z = self._encode(inputs, per_sample)
+    z = self._encode(inputs, per_sample, taps)
     if only_encode:
       return z
     q = torch.empty_like(z)
@@ -443,10 +477,10 @@ class AutoencoderVQ(_AutoencoderBase):
     loss = ((e - z) ** 2).mean() * (1.0 + self._beta)
     return q, loss, idx
 
-  def decode(self, latents, force_quantize=False, training=False, scale_factor=1.0):
+  def decode(self, latents, force_quantize=False, training=False, scale_factor=1.0, taps=None):
     """autoencoder.py:430-436."""
     x = torch.as_tensor(latents, dtype=torch.float32).to(self.device).contiguous()
-    return self._decoder.decode(x, scale_factor=scale_factor, force_quantize=force_quantize)
+    return self._decoder.decode(x, scale_factor=scale_factor, force_quantize=force_quantize, taps=taps)
 
   def call(self, inputs, return_indices=False, training=False):
     """autoencoder.py:438-444: (reconstruction, codebook loss[, code indices])."""

@@ -188,6 +188,8 @@ class UNet:
     self._attn_all = {}                   # every accumulator this model has handed out, by (st index, shape)
     self._fwd_index = None                # the device step counter of the evaluation in flight (forward(index=))
     self._pend = None
+    self._taps = None                     # forward(taps=): the dict this evaluation stores its stage outputs in
+    self._tapq = []                       # ... stage outputs that a deferred split-K product has yet to complete
     self._model_channels = model_channels
     self._out_channels = out_channels
     self._num_blocks = num_blocks
@@ -369,6 +371,26 @@ class UNet:
     if self._pend is not None:
       ops.finish(self._pend)
       self._pend = None
+    self._tap_drain()
+
+  # ---- stage taps (forward(taps=)): copies only, no launch of the evaluation moves ---------------------------
+  def _tap(self, name, t):
+    """Stores a clone of stage output `t`.  While a deferred split-K product is outstanding `t` may be the tensor
+    its slabs still have to be summed into: the clone is queued and made by the GroupNorm or flush that completes
+    the product (never by an early flush, which would replace ldm_groupnorm_splitk with the plain reduce) -- that
+    is before the next writer of the reused scratch tags (blk_r, blk_s), whose producer flushes first."""
+    if self._taps is None:
+      return
+    if self._pend is not None:
+      self._tapq.append((name, t))
+    else:
+      self._taps[name] = t.clone()
+
+  def _tap_drain(self):
+    if self._tapq:
+      for name, t in self._tapq:
+        self._taps[name] = t.clone()
+      self._tapq = []
 
   def _conv_deferred(self, x, wt, out, **kw):
     self._flush()
@@ -380,6 +402,7 @@ class UNet:
     pend, self._pend = self._pend, None
     ops.groupnorm(x, gn[0], gn[1], out, eps, silu=silu, partial=self._gnp, pending=pend, store_x=store_x,
                   fused=None if self._gn_single else False)
+    self._tap_drain()                     # (x is complete now: store_x is False only for a tensor no stage ends in)
     return out
 
   def _res(self, r, x, tall, out):
@@ -545,7 +568,7 @@ class UNet:
 
   # ---- forward ---------------------------------------------------------------------------------
   def forward(self, x, t_rows=None, steps=None, index=None, out=None, shared_t=False, paired_rows=False,
-              temb_table=None, pre_decrement=False, context_rows=None):
+              temb_table=None, pre_decrement=False, context_rows=None, taps=None):
     """x f32 [R,h,w,4].  Timestep either per row (`t_rows` int32 [R]) or, for the
     graph-replayed DDIM loop, `steps[*index]` for every row.  `shared_t=True` with
     t_rows declares that all rows carry t_rows[0].
@@ -558,7 +581,18 @@ class UNet:
     (one launch instead of four); `pre_decrement`: that launch first decrements *index, the DDIM loop's counter.
     `context_rows=(lo, hi)`: x has hi - lo rows and row r attends to row lo + r of the resident context (set_context
     projected more rows than this evaluation has): the conditional half (B, 2B) of a classifier-free-guidance batch on
-    its own.  The cross-attention launches read contiguous row slices of the projections."""
+    its own.  The cross-attention launches read contiguous row slices of the projections.
+    `taps` (a dict; eager only): the evaluation stores a clone of every stage's output in it, in the storage type,
+    under the stage's weight prefix -- conv_in, temb (the whole projected table), input_blocks/{i}/residual |
+    spatial_transformer | downsample, middle_block/residual1 | spatial_transformer | residual2,
+    output_blocks/{j}/residual | spatial_transformer | upsample, out.  The launches and their order are those of
+    the evaluation without taps, and so are the output's bits; on the shared prefix of `paired_rows` a stage has
+    R/2 rows and the tap holds those."""
+    if taps is not None:
+      if not isinstance(taps, dict):
+        raise ValueError("forward(taps=) takes a dict")
+      if torch.cuda.is_current_stream_capturing():
+        raise ValueError("forward(taps=) is eager only: a capturing stream cannot hand out clones")
     assert x.dtype == torch.float32 and x.is_contiguous()
     R, h, w, _ = x.shape
     nlev = max(self.skip_lvl)
@@ -581,6 +615,8 @@ class UNet:
     else:
       assert not pre_decrement
       tall = self._temb(R, t_rows, steps, index, shared_t)
+    self._taps, self._tapq = taps, []
+    self._tap("temb", tall)
     self._ctx_sel = None if context_rows is None else slice(lo, lo + R)
     self._fwd_index = index
     # a CFG pair: the launches in front of the first cross-attention once, on the first R/2 rows
@@ -611,14 +647,17 @@ class UNet:
           ops.cast(d0[:half], d0[half:])
         else:
           ops.conv3x3_small(x, self.conv_in[0], self.conv_in[1], skip(0))
+        self._tap("conv_in", skip(0))
         for i, blk in enumerate(self.in_blocks):
           cur, dst = skip(i), skip(i + 1)
           if blk[0] == "down":
             self._conv_deferred(cur, blk[1], dst, bias=blk[2], stride=2)     # (flushes first: it reads cur)
+            self._tap(f"input_blocks/{i}/downsample", dst)
             continue
           _, r, st = blk
           if st is None:
             self._res(r, cur, tall, dst)
+            self._tap(f"input_blocks/{i}/residual", dst)
           elif i == 0 and pair:
             # the pair's common prefix: ResBlock + the transformer block's head on the first R/2 rows, with the
             # launch plans of THAT row count; the block's tail (from the first cross-attention on) on all rows
@@ -626,39 +665,51 @@ class UNet:
             with ops.plan_scope(half, h, dt):
               tmp, tmp_full = self._pair_buf("blk_r", (half,) + tuple(dst.shape[1:3]) + (r.cout,), dt, True)
               self._res(r, cur[:half], tall if tall.shape[0] == 1 else tall[:half], tmp)
+              self._tap(f"input_blocks/{i}/residual", tmp)
               self._st(st, tmp, dst, pair=True, x_full=tmp_full)
+            self._tap(f"input_blocks/{i}/spatial_transformer", dst)
           else:
             tmp = B_.get("blk_r", (R,) + tuple(dst.shape[1:3]) + (r.cout,), dt)
             self._res(r, cur, tall, tmp)
+            self._tap(f"input_blocks/{i}/residual", tmp)
             self._st(st, tmp, dst)
+            self._tap(f"input_blocks/{i}/spatial_transformer", dst)
         cur = skip(n_in)
         r1, stm, r2 = self.mid
         shp = (R,) + tuple(cur.shape[1:3]) + (r1.cout,)
         m1 = self._res(r1, cur, tall, B_.get("blk_r", shp, dt))
+        self._tap("middle_block/residual1", m1)
         m2 = self._st(stm, m1, B_.get("blk_s", shp, dt))
+        self._tap("middle_block/spatial_transformer", m2)
         self._res(r2, m2, tall, cats[0][..., :r2.cout])
+        self._tap("middle_block/residual2", cats[0][..., :r2.cout])
         for j, (r, st, up) in enumerate(self.out_blocks):
           xin = cats[j]
           shp = (R, xin.shape[1], xin.shape[2], r.cout)
           dst = final if j + 1 == n_out else cats[j + 1][..., :r.cout]
           # the block's last stage writes dst, the ones before it scratch
           o = self._res(r, xin, tall, dst if st is None and up is None else B_.get("blk_r", shp, dt))
+          self._tap(f"output_blocks/{j}/residual", o)
           if st is not None:
             o = self._st(st, o, dst if up is None else B_.get("blk_s", shp, dt))
+            self._tap(f"output_blocks/{j}/spatial_transformer", o)
           if up is not None:
             self._flush()                                           # it reads o
             if self._phase_upsample:                                # unet.py:44-47
               ops.conv3x3_up2(o, up[0], dst, bias=up[1])
             else:
               ops.conv3x3(o, up[0], dst, bias=up[1], upsample=True)
+            self._tap(f"output_blocks/{j}/upsample", dst)
         t0 = B_.get("gn", tuple(final.shape), dt)
         self._gn(final, self.gn_out, GN_EPS_RES, True, t0)
         if self.conv_out_mm is not None:
           ops.conv3x3(t0, self.conv_out_mm, out, bias=self.conv_out[1])
         else:
           ops.conv3x3_small(t0, self.conv_out[0], self.conv_out[1], out)
+        self._tap("out", out)
       finally:
         self._flush()
+        self._taps, self._tapq = None, []
     return out
 
   def temb_table(self, steps):

@@ -87,6 +87,15 @@ def test_unet_forward(dev, dtype, unet_w):
   # second call with the same context object re-uses the cached K/V and is deterministic
   got2 = unet(torch.from_numpy(x), torch.from_numpy(t), torch.from_numpy(ctx))
   assert torch.equal(got, got2)
+  # the oracle's per-block taps against the model's own (free-running, the same gate; the stage-local comparison is
+  # tests/test_zz_block_parity_gpu.py): a block's tap is its last stage's
+  mine = {}
+  got3 = unet.forward(torch.from_numpy(x).to(dev), t_rows=torch.from_numpy(t).to(dev), taps=mine)
+  assert torch.equal(got, got3)
+  for blk, want in taps.items():
+    last = [n for n in mine if n.startswith(blk + "/")][-1]
+    assert last.rsplit("/", 1)[1] in ("residual", "spatial_transformer", "downsample", "upsample", "residual2")
+    check(mine[last], want, dtype, f"unet tap {last}")
 
 
 @pytest.mark.parametrize("dtype", DT)
