@@ -459,15 +459,20 @@ def linear(x, wt, out, bias=None, act=ACT_NONE, residual=None, addend=None, add_
   return out
 
 
+def linear_t_shape_supported(dtype, K, N, rows, ld, stride):
+  """`linear_t_supported` of shapes alone: `rows` per group, the transposed output's row length `ld` and group
+  stride `stride` (persistent kernel: bf16, N a multiple of 128 or 160, groups of rows that are multiples of 32)."""
+  return (dtype == torch.bfloat16 and K % 64 == 0 and (N % 128 == 0 or N % 160 == 0) and rows % 32 == 0 and
+          ld % 8 == 0 and stride % 8 == 0)
+
+
 def linear_t_supported(x, wt, out_t):
-  """True if `linear_t` can run this product (persistent kernel: bf16, N a multiple of 128 or 160,
-  groups of rows that are multiples of 32)."""
+  """True if `linear_t` can run this product."""
   K, N = x.shape[-1], wt.shape[0]
   M = x.numel() // K
   G = out_t.shape[0]
-  return (x.dtype == torch.bfloat16 and out_t.dtype == torch.bfloat16 and K % 64 == 0 and
-          (N % 128 == 0 or N % 160 == 0) and M % G == 0 and (M // G) % 32 == 0 and out_t.stride(2) == 1 and
-          out_t.stride(1) % 8 == 0 and out_t.stride(0) % 8 == 0)
+  return (out_t.dtype == x.dtype and M % G == 0 and out_t.stride(2) == 1 and
+          linear_t_shape_supported(x.dtype, K, N, M // G, out_t.stride(1), out_t.stride(0)))
 
 
 def linear_t(x, wt, out_t, tile=0, bias=None, ln_fold=None):

@@ -23,11 +23,14 @@ changes results beyond float rounding order):
 """
 from __future__ import annotations
 
+from typing import NamedTuple, Optional
+
 import numpy as np
 import torch
 
 from . import layout as L
 from . import ops
+from .st_form import StFlags, StForm, st_form
 from .weights import init_weights, unet_manifest
 
 GN_EPS_RES = 1e-5   # unet.py:374,377,115
@@ -128,6 +131,22 @@ class _ST:
     if self.fold is not None and c == 320:
       self.ffn_aux = L.ffn_aux(self.fold["geglu"][1], self.fold["geglu"][2])
     self.ctx_k = self.ctx_vt = None     # filled by UNet.set_context
+    self.form = None                    # the StForm of the last evaluation (UNet._st)
+
+
+class _StRun(NamedTuple):
+  """What the launches after a block's self-attention read: the block, its form, the self-attention's output, the
+  residual stream and the block input (all of out's rows, or half of them for ldm_st_block's in_rows), the block
+  output, the context's projections, the heat-map setting or None."""
+  st: _ST
+  form: StForm
+  att: torch.Tensor
+  ha: torch.Tensor
+  x: torch.Tensor
+  out: torch.Tensor
+  ctx_k: torch.Tensor
+  ctx_vt: torch.Tensor
+  cap: Optional[dict]
 
 
 class UNet:
@@ -145,39 +164,17 @@ class UNet:
                ffn_min_rows=24576, fused_tail=True, fused_xattn=True, fused_block=True,
                shared_prefix=True, merge_qkv=True, merge_qkv_max_rows=1 << 30,
                merge_shortcut=True, merge_ffproj=True, block_min_rows=12288, phase_upsample=True):
-    # fuse_layernorm: the transformer blocks' LayerNorms come out of the producing GEMM's epilogue
-    # where its tile holds whole rows (C = 320).  Measured on MI355X at R=32: 11.02 vs 10.95 ms per
-    # step -- the whole-row 128x320 tile (one workgroup per CU) plus the extra epilogue pass cost
-    # slightly more than the 15 LayerNorm launches they replace.  Opt-in (parity-tested).
-    self._fuse_ln = bool(fuse_layernorm)
-    # fuse_qkv: the self-attention q|k and v projections as one GEMM launch with a transposed second
-    # output (ldm_gemm out2)
-    self._fuse_qkv = bool(fuse_qkv)
-    # bf16: q|k and v as two persistent-kernel launches (v stored transposed); split_qkv=False: A/B
-    self._split_qkv = dtype == torch.bfloat16 and bool(split_qkv)
+    # the transformer blocks' launch-form switches and thresholds (st_form.StFlags holds what each one selects)
+    self._st_flags = StFlags.of(dtype, fuse_layernorm=fuse_layernorm, fuse_qkv=fuse_qkv, split_qkv=split_qkv,
+                                fold_layernorm=fold_layernorm, matrix_softmax=matrix_softmax, fused_ffn=fused_ffn,
+                                fused_tail=fused_tail, fused_xattn=fused_xattn, fused_block=fused_block,
+                                merge_qkv=merge_qkv, merge_qkv_max_rows=merge_qkv_max_rows, merge_ffproj=merge_ffproj,
+                                fold_min_rows=fold_min_rows, ffn_min_rows=ffn_min_rows, block_min_rows=block_min_rows)
+    self._fuse_ln = self._st_flags.fuse_ln
     self._small_conv_out = bool(small_conv_out)
-    # bf16: each LayerNorm of the transformer blocks (unet.py:309-313) is folded into the projection it
-    # feeds -- LN(x) W^T = rstd (x (gamma (.) W)^T - mean colsum) + W beta -- and the persistent GEMM derives
-    # the row statistics from the A tiles it stages anyway: 48 LayerNorm launches and their normalised
-    # copies of the residual stream disappear.  Only where the launch has enough rows to fill the chip
-    # on the persistent kernel (fold_min_rows); float32 keeps the separate LayerNorm (parity mode).
-    self._fold_ln = dtype == torch.bfloat16 and bool(fold_layernorm) and not self._fuse_ln
-    self._fold_min_rows = int(fold_min_rows)
-    self._matrix_softmax = bool(matrix_softmax)   # ldm_attention_ms on the 40-wide heads (with the fold; A/B: False)
-    self._fused_ffn = bool(fused_ffn)             # ldm_ffn_geglu on the C = 320 blocks (needs the fold; A/B: False)
-    self._fused_tail = bool(fused_tail)           # ... with the o-projection before and proj_out after it (ldm_st_tail)
-    self._fused_block = bool(fused_block)         # ... and o1-projection + query projection in front (ldm_st_block)
-    self._fused_xattn = bool(fused_xattn)         # ... and the cross-attention in front of the tail (ldm_st_xtail)
-    self._block_min_rows = int(block_min_rows)    # ... ldm_st_block alone from 192 panels of 64 rows on
-    self._ffn_min_rows = int(ffn_min_rows)        # ... from 192 panels of 128 rows on (3/4 of the CUs busy)
     self._gn_single = bool(gn_single_launch)      # False: partial-sums + apply launches everywhere (A/B)
     self._defer_reduce = bool(defer_reduce)   # split-K reduces fused into the consuming GroupNorm (A/B: False)
-    self._merge_ffproj = bool(merge_ffproj)       # FF-out + proj_out as one folded product on the per-layer path (bf16; A/B: False)
     self._merge_shortcut = bool(merge_shortcut)   # ResBlock shortcut inside its second convolution's K loop (A/B: False)
-    self._merge_qkv = bool(merge_qkv)             # LayerNorm-folded q | k | V^T as one launch (A/B: False = two)
-    # (a row limit from the first form of the launch, whose workgroups lay on one side of n_split and could not be
-    # balanced at M = 32768: 6 + 3 n-tiles on 2 workgroups per panel; ranges may straddle n_split now)
-    self._merge_qkv_max_rows = int(merge_qkv_max_rows)
     # the upsample convolutions as four 2x2 phase convolutions over the image itself (ops.conv3x3_up2: 4/9 of the
     # multiply-adds; only that weight form is built).  A/B: False = the nine-tap gather over the upsampled image
     self._phase_upsample = bool(phase_upsample)
@@ -224,7 +221,7 @@ class UNet:
       return r
 
     def mk_st(p):
-      return (_ST(w, p, H, dt, dev, fold_ln=self._fold_ln, matrix_softmax=self._matrix_softmax)
+      return (_ST(w, p, H, dt, dev, fold_ln=self._st_flags.fold_ln, matrix_softmax=self._st_flags.matrix_softmax)
               if (p + "/dense1/kernel") in w else None)
 
     self.in_blocks, self.skip_ch, self.skip_lvl = [], [mc], [0]
@@ -394,9 +391,12 @@ class UNet:
 
   def _conv_deferred(self, x, wt, out, **kw):
     self._flush()
-    r = ops.conv3x3(x, wt, out, defer_reduce=self._defer_reduce, **kw)
-    self._pend = r if isinstance(r, ops.PendingReduce) else None
+    self._park(ops.conv3x3(x, wt, out, defer_reduce=self._defer_reduce, **kw))
     return out
+
+  def _park(self, r):
+    """`r`: what a launch with defer_reduce returned -- its slabs if the plan split K, for `_gn` or `_flush`."""
+    self._pend = r if isinstance(r, ops.PendingReduce) else None
 
   def _gn(self, x, gn, eps, silu, out, store_x=True):
     pend, self._pend = self._pend, None
@@ -444,127 +444,184 @@ class UNet:
     return full
 
   def _st(self, st, x, out, pair=False, x_full=None):
-    """`pair`: x holds the first half of out's rows and the second half is identical up to the first
-    cross-attention (forward(paired_rows=True)); out and the context cover all rows."""
-    B_, dt = self.buf, self.dtype
+    """One transformer block (unet.py:341-365): pick its form (st_form), run the head up to the self-attention, then
+    the form's way to the block's output.  `pair`: x holds the first half of out's rows and the second half is
+    identical up to the first cross-attention (forward(paired_rows=True)); out and the context cover all rows, and
+    `x_full` is x's buffer with room for them."""
+    R, h, w, c = x.shape
+    ctx_k, ctx_vt = (st.ctx_k, st.ctx_vt) if self._ctx_sel is None else (st.ctx_k[self._ctx_sel], st.ctx_vt[self._ctx_sel])
+    assert ctx_k.shape[0] == (2 * R if pair else R) and out.shape[0] == ctx_k.shape[0]
+    cap = self._attn_cap if self._attn_cap is not None and st.index in self._attn_cap["layers"] else None
+    form = st.form = st_form(self._st_flags, self.dtype, c, st.heads, st.s, st.sp, st.fold is not None,
+                             st.ffn_aux is not None, st.ffp is not None, st.ms, R, pair, h * w, ctx_k.shape[1],
+                             ctx_vt.shape[2], cap is not None)
+    (att, att_full), (ha, ha_full) = self._st_head(st, form, x, pair)
+    if form.leave_prefix:
+      # per-layer path: the pair leaves its common prefix here -- both halves get their copy of the self-attention's
+      # output, the residual stream and the block input, and everything below covers all rows
+      ins = self._dup_rows(att_full), self._dup_rows(ha_full), self._dup_rows(x_full)
+    else:
+      ins = att, ha, x                    # ("block" with a pair: half of out's rows -> ldm_st_block's in_rows)
+    self._ST_REST[form.rest](self, _StRun(st, form, *ins, out, ctx_k, ctx_vt, cap))
+    return out
+
+  def _ln_buf(self, like):
+    return self.buf.get("st_ln", tuple(like.shape), self.dtype)
+
+  def _lnp(self, st, form, i, hn):
+    """`ln=` of the GEMM that produces the residual stream `hn`: each LayerNorm of the block normalises a row the
+    preceding projection has just produced, so where the GEMM tile holds whole rows it is emitted by that GEMM's
+    epilogue (the "epilogue" form); else None."""
+    return (st.ln[i][0], st.ln[i][1], self._ln_buf(hn), LN_EPS) if form.norm == "epilogue" else None
+
+  def _normed(self, st, form, i, hn):
+    """LayerNorm i of the residual stream `hn` for a consumer without the fold: its own launch ("separate") unless
+    the GEMM that produced `hn` has emitted it."""
+    ln = self._ln_buf(hn)
+    if form.norm == "separate":
+      ops.layernorm(hn, st.ln[i][0], st.ln[i][1], ln, LN_EPS)
+    return ln
+
+  def _st_head(self, st, form, x, pair):
+    """GroupNorm, proj_in, the self-attention's projections in the form's norm / qkv arm and the self-attention
+    (unet.py:355-357, :309-310): (attention output, residual stream), each as _pair_buf's (view, full)."""
+    B_, dt, fold = self.buf, self.dtype, st.fold
     R, h, w, c = x.shape
     T, hs = h * w, st.heads * st.sp
-    scale = st.s ** -0.5
     t0 = B_.get("gn", (R, h, w, c), dt)
     self._gn(x, st.gn, GN_EPS_ST, False, t0)
     ha, ha_full = self._pair_buf("st_a", (R, T, c), dt, pair)
-    ln = B_.get("st_ln", (R, T, c), dt)
-    # each LayerNorm of the block normalises a row the preceding projection has just produced:
-    # where the GEMM tile holds whole rows (C = 320) it is emitted by that GEMM's epilogue
-    fuse_ln = self._fuse_ln and ops.linear_ln_supported(c, dt)
-    lnp = lambda i: (st.ln[i][0], st.ln[i][1], ln, LN_EPS) if fuse_ln else None
-    ops.linear(t0, st.proj_in[0], ha, bias=st.proj_in[1], ln=lnp(0))
+    ops.linear(t0, st.proj_in[0], ha, bias=st.proj_in[1], ln=self._lnp(st, form, 0, ha))
     qk = B_.get("st_qk", (R, T, 2 * hs), dt)
-    tp = (T + 7) // 8 * 8
-    vt = B_.get("st_vt", (R, hs, tp), dt, zero=True)
-    # LayerNorm folded into its consumer (bf16, launches with enough rows for the persistent kernel)
-    fold = st.fold if (st.fold is not None and R * T >= self._fold_min_rows and T % 32 == 0) else None
-    # self-attention (unet.py:309-310)
-    if fold is None and not fuse_ln:
-      ops.layernorm(ha, st.ln[0][0], st.ln[0][1], ln, LN_EPS)
-    if fold is not None and self._merge_qkv and R * T <= self._merge_qkv_max_rows and hs % 128 == 0:
+    vt = B_.get("st_vt", (R, hs, (T + 7) // 8 * 8), dt, zero=True)
+    if form.qkv == "qkv_fold":
       # q | k | V^T: one pass of the persistent kernel over the LayerNorm'ed rows (gemm3_kernel EPI bit 7)
       ops.linear(ha, fold["qkv1"][0], qk, bias=fold["qkv1"][2], ln_fold=(fold["qkv1"][1], LN_EPS), out2=vt)
-    elif fold is not None:
+    elif form.qkv == "qk_v_fold":
       ops.linear(ha, fold["qk1"][0], qk, bias=fold["qk1"][2], ln_fold=(fold["qk1"][1], LN_EPS))
       ops.linear_t(ha, fold["v1"][0], vt, bias=fold["v1"][2], ln_fold=(fold["v1"][1], LN_EPS))
-    elif self._split_qkv and ops.linear_t_supported(ln, st.v1, vt):
-      # bf16: q|k row-major and v TRANSPOSED (straight into the attention kernel's V^T layout) as two
-      # launches that can both take the persistent kernel (ops.linear_t)
-      ops.linear(ln, st.qk1, qk)
-      ops.linear_t(ln, st.v1, vt)
-    elif self._fuse_qkv and T % 4 == 0:
-      # q | k | v in ONE launch: q|k row-major, v straight into the attention kernel's V^T layout
-      ops.linear(ln, st.qkv1, qk, out2=vt)
     else:
-      ops.linear(ln, st.qk1, qk)
-      ops.bmm_nt(ln, st.v1, vt, transposed_out=True)
+      ln = self._normed(st, form, 0, ha)
+      if form.qkv == "qk_vt":
+        # bf16: q|k row-major and v TRANSPOSED (straight into the attention kernel's V^T layout) as two
+        # launches that can both take the persistent kernel (ops.linear_t)
+        ops.linear(ln, st.qk1, qk)
+        ops.linear_t(ln, st.v1, vt)
+      elif form.qkv == "qkv_out2":
+        # q | k | v in ONE launch: q|k row-major, v straight into the attention kernel's V^T layout
+        ops.linear(ln, st.qkv1, qk, out2=vt)
+      else:
+        ops.linear(ln, st.qk1, qk)
+        ops.bmm_nt(ln, st.v1, vt, transposed_out=True)
     att, att_full = self._pair_buf("st_att", (R, T, hs), dt, pair)
-    ms = fold is not None and st.ms
-    ops.attention(qk[..., :hs], qk[..., hs:], vt, att, st.heads, st.sp, scale, matrix_softmax=ms)
-    ctx_k, ctx_vt = (st.ctx_k, st.ctx_vt) if self._ctx_sel is None else (st.ctx_k[self._ctx_sel], st.ctx_vt[self._ctx_sel])
-    Ro = ctx_k.shape[0]                   # rows of `out` (= 2 R for a pair)
-    assert Ro == (2 * R if pair else R) and out.shape[0] == Ro
-    panel = (fold is not None and st.ffn_aux is not None and self._fused_ffn and Ro * T >= self._ffn_min_rows)
-    xtail = (panel and self._fused_tail and self._fused_xattn and ms and hs == 384 and T % 128 == 0
-             and ctx_k.shape[1] <= 80 and ctx_vt.shape[2] >= 80)
-    # ldm_st_block has a 64-row panel form for launches below 192 panels of 128 rows (round 4): it pays from 192
-    # panels of 64 rows on (`block_min_rows`), where the other row-panel launches (128-row panels only) do not
-    blk = (self._fused_block and fold is not None and st.ffn_aux is not None and self._fused_ffn and self._fused_tail
-           and self._fused_xattn and ms and hs == 384 and T % 128 == 0 and ctx_k.shape[1] <= 80 and ctx_vt.shape[2] >= 80
-           and Ro * T >= min(self._ffn_min_rows, self._block_min_rows))
-    cap = self._attn_cap if self._attn_cap is not None and st.index in self._attn_cap["layers"] else None
-    blk = blk and cap is None             # (ldm_st_block never materialises the queries the heat maps read)
-    if pair and not blk:
-      # per-layer path: the pair leaves its common prefix here -- both halves get their copy of the self-attention's
-      # output, the residual stream and the block input, and everything below covers all rows
-      att, ha, x = self._dup_rows(att_full), self._dup_rows(ha_full), self._dup_rows(x_full)
-      R = Ro
-      ln = B_.get("st_ln", (R, T, c), dt)
-      lnp = lambda i: (st.ln[i][0], st.ln[i][1], ln, LN_EPS) if fuse_ln else None
-    hb = B_.get("st_b", (R, T, c), dt)
-    q = B_.get("st_q", (R, T, hs), dt)
-    if blk:
-      # everything from the self-attention's output to the block's output: ONE row-panel launch (ldm_st_block)
-      ops.st_block(att, st.o1[0], st.o1[1], ha, fold["q2"][0], fold["q2"][1], fold["q2"][2], ctx_k, ctx_vt,
-                   st.o2[0], st.o2[1], fold["geglu"][0], st.ffn_aux, st.ff_out[0], st.ff_out[1], st.proj_out[0],
-                   st.proj_out[1], x, out, LN_EPS)      # (pair: att / ha / x hold half of out's rows -> in_rows)
-      return out
-    ops.linear(att, st.o1[0], hb, bias=st.o1[1], residual=ha, ln=lnp(1))
-    # cross-attention (unet.py:311-312)
-    if fold is not None:
-      ops.linear(hb, fold["q2"][0], q, bias=fold["q2"][2], ln_fold=(fold["q2"][1], LN_EPS))
+    ops.attention(qk[..., :hs], qk[..., hs:], vt, att, st.heads, st.sp, st.s ** -0.5, matrix_softmax=form.ms)
+    return (att, att_full), (ha, ha_full)
+
+  # ---- the six ways from the self-attention's output to the block's output (StForm.rest), each a prefix of launches
+  # shared with the next one down plus its own: b = _StRun
+  def _st_block(self, b):
+    """Everything as ONE row-panel launch (ldm_st_block)."""
+    st, q2 = b.st, b.st.fold["q2"]
+    ops.st_block(b.att, st.o1[0], st.o1[1], b.ha, q2[0], q2[1], q2[2], b.ctx_k, b.ctx_vt, st.o2[0], st.o2[1],
+                 st.fold["geglu"][0], st.ffn_aux, st.ff_out[0], st.ff_out[1], st.proj_out[0], st.proj_out[1], b.x, b.out,
+                 LN_EPS)
+
+  def _st_query(self, b):
+    """o1-projection + residual, the cross-attention's queries (unet.py:310-311) and, captured, their heat map:
+    (residual stream, queries)."""
+    st = b.st
+    hb = self.buf.get("st_b", tuple(b.ha.shape), self.dtype)
+    q = self.buf.get("st_q", tuple(b.att.shape), self.dtype)
+    ops.linear(b.att, st.o1[0], hb, bias=st.o1[1], residual=b.ha, ln=self._lnp(st, b.form, 1, hb))
+    if b.form.norm == "fold":
+      q2 = st.fold["q2"]
+      ops.linear(hb, q2[0], q, bias=q2[2], ln_fold=(q2[1], LN_EPS))
     else:
-      if not fuse_ln:
-        ops.layernorm(hb, st.ln[1][0], st.ln[1][1], ln, LN_EPS)
-      ops.linear(ln, st.q2, q)
-    if cap is not None:
-      self._attn_map(st, cap, q, ctx_k, h, w, scale, ms)
-    if xtail:
-      # ... with the cross-attention itself in front of it, in place in the LDS panel
-      ops.st_xtail(q, ctx_k, ctx_vt, st.o2[0], st.o2[1], hb, fold["geglu"][0], st.ffn_aux, st.ff_out[0],
-                   st.ff_out[1], st.proj_out[0], st.proj_out[1], x, out, LN_EPS)
-      return out
-    ops.attention(q, ctx_k, ctx_vt, att, st.heads, st.sp, scale, matrix_softmax=ms)
-    if panel and self._fused_tail and hs == 384:
-      # o-projection + residual, LayerNorm -> GEGLU -> FF-out + residual, proj_out + residual: ONE row-panel
-      # launch; the two intermediate residual-stream tensors live only in LDS (unet.py:312-313, :363-365)
-      ops.st_tail(att, st.o2[0], st.o2[1], hb, fold["geglu"][0], st.ffn_aux, st.ff_out[0], st.ff_out[1],
-                  st.proj_out[0], st.proj_out[1], x, out, LN_EPS)
-      return out
-    ops.linear(att, st.o2[0], ha, bias=st.o2[1], residual=hb, ln=lnp(2))
-    # GEGLU feed-forward (unet.py:313, :323-325, :335-338)
-    if panel:
-      # LayerNorm -> GEGLU -> FF-out + residual as ONE row-panel launch: the [R*T, 4C] hidden activation
-      # never reaches HBM (unet.py:313)
-      ops.ffn_geglu(ha, fold["geglu"][0], st.ffn_aux, st.ff_out[0], st.ff_out[1], hb, LN_EPS)
-      ops.linear(hb, st.proj_out[0], out, bias=st.proj_out[1], residual=x)
-      return out
-    ff = B_.get("st_ff", (R, T, 4 * c), dt)
-    if fold is not None:
-      ops.linear(ha, fold["geglu"][0], ff, bias=fold["geglu"][2], act=ops.ACT_GEGLU,
-                 ln_fold=(fold["geglu"][1], LN_EPS))
+      ops.linear(self._normed(st, b.form, 1, hb), st.q2, q)
+    if b.cap is not None:
+      self._attn_map(st, b.cap, q, b.ctx_k, b.x.shape[1], b.x.shape[2], st.s ** -0.5, b.form.ms)
+    return hb, q
+
+  def _st_xtail(self, b):
+    """... with the cross-attention itself in front of the tail, in place in the LDS panel (ldm_st_xtail)."""
+    st = b.st
+    hb, q = self._st_query(b)
+    ops.st_xtail(q, b.ctx_k, b.ctx_vt, st.o2[0], st.o2[1], hb, st.fold["geglu"][0], st.ffn_aux, st.ff_out[0],
+                 st.ff_out[1], st.proj_out[0], st.proj_out[1], b.x, b.out, LN_EPS)
+
+  def _st_cross(self, b):
+    """... the cross-attention as its own launch, into b.att (unet.py:311-312): the residual stream."""
+    hb, q = self._st_query(b)
+    ops.attention(q, b.ctx_k, b.ctx_vt, b.att, b.st.heads, b.st.sp, b.st.s ** -0.5, matrix_softmax=b.form.ms)
+    return hb
+
+  def _st_tail(self, b):
+    """o-projection + residual, LayerNorm -> GEGLU -> FF-out + residual, proj_out + residual: ONE row-panel launch;
+    the two intermediate residual-stream tensors live only in LDS (ldm_st_tail; unet.py:312-313, :363-365)."""
+    st = b.st
+    hb = self._st_cross(b)
+    ops.st_tail(b.att, st.o2[0], st.o2[1], hb, st.fold["geglu"][0], st.ffn_aux, st.ff_out[0], st.ff_out[1],
+                st.proj_out[0], st.proj_out[1], b.x, b.out, LN_EPS)
+
+  def _st_o2(self, b):
+    """... the o-projection + residual as its own launch, into b.ha: the scratch the stream has left."""
+    hb = self._st_cross(b)
+    ops.linear(b.att, b.st.o2[0], b.ha, bias=b.st.o2[1], residual=hb, ln=self._lnp(b.st, b.form, 2, b.ha))
+    return hb
+
+  def _st_ffn(self, b):
+    """LayerNorm -> GEGLU -> FF-out + residual as ONE row-panel launch: the [R*T, 4C] hidden activation never
+    reaches HBM (ldm_ffn_geglu; unet.py:313)."""
+    st = b.st
+    hb = self._st_o2(b)
+    ops.ffn_geglu(b.ha, st.fold["geglu"][0], st.ffn_aux, st.ff_out[0], st.ff_out[1], hb, LN_EPS)
+    ops.linear(hb, st.proj_out[0], b.out, bias=st.proj_out[1], residual=b.x)
+
+  def _st_geglu(self, b):
+    """... the GEGLU projection as its own launch (unet.py:313, :323-325, :335-338): (scratch, hidden activation)."""
+    st = b.st
+    hb = self._st_o2(b)
+    ff = self.buf.get("st_ff", tuple(b.ha.shape[:2]) + (4 * st.c,), self.dtype)
+    if b.form.norm == "fold":
+      g = st.fold["geglu"]
+      ops.linear(b.ha, g[0], ff, bias=g[2], act=ops.ACT_GEGLU, ln_fold=(g[1], LN_EPS))
     else:
-      if not fuse_ln:
-        ops.layernorm(ha, st.ln[2][0], st.ln[2][1], ln, LN_EPS)
-      ops.linear(ln, st.geglu[0], ff, bias=st.geglu[1], act=ops.ACT_GEGLU)
-    if st.ffp is not None and self._merge_ffproj:
-      # y = h + FF-out(ff) and proj_out(y) + x are two linear layers with a residual between them: ONE product over
-      # (ff | h) with the folded weights (Wp W2 | Wp) -- no proj_out launch, no y tensor (unet.py:313, :363-365)
-      # (its split-K reduce is left to the GroupNorm that reads `out` next -- the following ResBlock's, on the way
-      # down -- like a convolution's; whatever else comes next flushes it as a plain reduce)
-      self._flush()
-      r = ops.linear(ff, st.ffp[0], out, bias=st.ffp[1], residual=x, x2=ha, defer_reduce=self._defer_reduce)
-      self._pend = r if isinstance(r, ops.PendingReduce) else None
-      return out
-    ops.linear(ff, st.ff_out[0], hb, bias=st.ff_out[1], residual=ha)
-    ops.linear(hb, st.proj_out[0], out, bias=st.proj_out[1], residual=x)
-    return out
+      ops.linear(self._normed(st, b.form, 2, b.ha), st.geglu[0], ff, bias=st.geglu[1], act=ops.ACT_GEGLU)
+    return hb, ff
+
+  def _st_ffproj(self, b):
+    """y = h + FF-out(ff) and proj_out(y) + x are two linear layers with a residual between them: ONE product over
+    (ff | h) with the folded weights (Wp W2 | Wp) -- no proj_out launch, no y tensor (unet.py:313, :363-365).  Its
+    split-K reduce is left to the GroupNorm that reads `out` next -- the following ResBlock's, on the way down --
+    like a convolution's; whatever else comes next flushes it as a plain reduce."""
+    _, ff = self._st_geglu(b)
+    self._flush()
+    self._park(ops.linear(ff, b.st.ffp[0], b.out, bias=b.st.ffp[1], residual=b.x, x2=b.ha,
+                          defer_reduce=self._defer_reduce))
+
+  def _st_layers(self, b):
+    """FF-out + residual and proj_out + residual, a launch each."""
+    st = b.st
+    hb, ff = self._st_geglu(b)
+    ops.linear(ff, st.ff_out[0], hb, bias=st.ff_out[1], residual=b.ha)
+    ops.linear(hb, st.proj_out[0], b.out, bias=st.proj_out[1], residual=b.x)
+
+  _ST_REST = dict(block=_st_block, xtail=_st_xtail, tail=_st_tail, ffn=_st_ffn, ffproj=_st_ffproj, layers=_st_layers)
+
+  def forms(self):
+    """[(st index, StForm)]: the form each transformer block took in the last evaluation that reached it."""
+    return [(st.index, st.form) for st in self.sts if st.form is not None]
+
+  def _res_st(self, prefix, r, st, x, tall, dst, last=True, res="residual"):
+    """ResBlock, then the level's transformer block where it has one, a tap after each.  The last of them writes
+    `dst` if nothing of the block follows it (`last`), every other stage scratch.  Returns that last output."""
+    scratch = lambda tag: self.buf.get(tag, tuple(x.shape[:3]) + (r.cout,), self.dtype)
+    o = self._res(r, x, tall, dst if st is None and last else scratch("blk_r"))
+    self._tap(f"{prefix}/{res}", o)
+    if st is not None:
+      o = self._st(st, o, dst if last else scratch("blk_s"))
+      self._tap(f"{prefix}/spatial_transformer", o)
+    return o
 
   # ---- forward ---------------------------------------------------------------------------------
   def forward(self, x, t_rows=None, steps=None, index=None, out=None, shared_t=False, paired_rows=False,
@@ -655,10 +712,7 @@ class UNet:
             self._tap(f"input_blocks/{i}/downsample", dst)
             continue
           _, r, st = blk
-          if st is None:
-            self._res(r, cur, tall, dst)
-            self._tap(f"input_blocks/{i}/residual", dst)
-          elif i == 0 and pair:
+          if i == 0 and pair:
             # the pair's common prefix: ResBlock + the transformer block's head on the first R/2 rows, with the
             # launch plans of THAT row count; the block's tail (from the first cross-attention on) on all rows
             self._flush()
@@ -669,30 +723,14 @@ class UNet:
               self._st(st, tmp, dst, pair=True, x_full=tmp_full)
             self._tap(f"input_blocks/{i}/spatial_transformer", dst)
           else:
-            tmp = B_.get("blk_r", (R,) + tuple(dst.shape[1:3]) + (r.cout,), dt)
-            self._res(r, cur, tall, tmp)
-            self._tap(f"input_blocks/{i}/residual", tmp)
-            self._st(st, tmp, dst)
-            self._tap(f"input_blocks/{i}/spatial_transformer", dst)
-        cur = skip(n_in)
+            self._res_st(f"input_blocks/{i}", r, st, cur, tall, dst)
         r1, stm, r2 = self.mid
-        shp = (R,) + tuple(cur.shape[1:3]) + (r1.cout,)
-        m1 = self._res(r1, cur, tall, B_.get("blk_r", shp, dt))
-        self._tap("middle_block/residual1", m1)
-        m2 = self._st(stm, m1, B_.get("blk_s", shp, dt))
-        self._tap("middle_block/spatial_transformer", m2)
+        m2 = self._res_st("middle_block", r1, stm, skip(n_in), tall, None, last=False, res="residual1")
         self._res(r2, m2, tall, cats[0][..., :r2.cout])
         self._tap("middle_block/residual2", cats[0][..., :r2.cout])
         for j, (r, st, up) in enumerate(self.out_blocks):
-          xin = cats[j]
-          shp = (R, xin.shape[1], xin.shape[2], r.cout)
           dst = final if j + 1 == n_out else cats[j + 1][..., :r.cout]
-          # the block's last stage writes dst, the ones before it scratch
-          o = self._res(r, xin, tall, dst if st is None and up is None else B_.get("blk_r", shp, dt))
-          self._tap(f"output_blocks/{j}/residual", o)
-          if st is not None:
-            o = self._st(st, o, dst if up is None else B_.get("blk_s", shp, dt))
-            self._tap(f"output_blocks/{j}/spatial_transformer", o)
+          o = self._res_st(f"output_blocks/{j}", r, st, cats[j], tall, dst, last=up is None)
           if up is not None:
             self._flush()                                           # it reads o
             if self._phase_upsample:                                # unet.py:44-47

@@ -69,6 +69,26 @@ FORMS_F32 = {
                        _fewer_layernorms),
     "two-launch-shortcut": (dict(merge_shortcut=False), (), ("ldm_attention_ms",) + PANEL, _gemms(N_SHORTCUT_A)),
 }
+# name -> {C: (norm, qkv, ms, rest)}: the StForm (ldm_tf2_amd/st_form.py) each of model A's blocks must pick at these
+# shapes -- C = 320 at T = 256 (40-wide heads), C = 640 at T = 64 (no ldm_ffn_geglu weights: the per-layer rest)
+_D320, _D640 = ("fold", "qkv_fold", True, "block"), ("fold", "qkv_fold", False, "ffproj")
+PICKED_BF16 = {
+    "default": {320: _D320, 640: _D640},
+    "xtail": {320: _D320[:3] + ("xtail",), 640: _D640},
+    "tail": {320: _D320[:3] + ("tail",), 640: _D640},
+    "ffn": {320: _D320[:3] + ("ffn",), 640: _D640},
+    "merged-ffproj": {320: _D320[:3] + ("ffproj",), 640: _D640},
+    "split-ffproj": {320: _D320[:3] + ("layers",), 640: _D640[:3] + ("layers",)},
+    "no-matrix-softmax": {320: ("fold", "qkv_fold", False, "tail"), 640: _D640},
+    "split-qkv": {320: ("fold", "qk_v_fold", True, "block"), 640: ("fold", "qk_v_fold", False, "ffproj")},
+    "no-fold": {320: ("separate", "qk_vt", False, "layers"), 640: ("separate", "qk_vt", False, "layers")},
+    "fuse-layernorm": {320: ("epilogue", "qk_vt", False, "layers"), 640: ("separate", "qk_vt", False, "layers")},
+    "no-defer": {320: _D320, 640: _D640}, "gn-two-launch": {320: _D320, 640: _D640},
+    "two-launch-shortcut": {320: _D320, 640: _D640}, "gather-upsample": {320: _D320, 640: _D640},
+}
+_F32 = ("separate", "qkv_out2", False, "layers")
+PICKED_F32 = {"default": {320: _F32, 640: _F32}, "fuse-layernorm": {320: ("epilogue",) + _F32[1:], 640: _F32},
+              "two-launch-shortcut": {320: _F32, 640: _F32}}
 CASES = [("A", BF16, n, "plain") for n in FORMS_BF16]
 CASES += [("A", BF16, n, "paired") for n in ("default", "xtail", "tail", "ffn")]
 CASES += [("A", BF16, "default", "context_rows")]
@@ -97,7 +117,8 @@ def _launches(calls):
 
 
 def _evaluate(dev, monkeypatch, model, dtype, kw, form):
-  """(calls, number of phase-upsample launches, taps, env): one model build, the evaluation without and with taps."""
+  """(calls, number of phase-upsample launches, taps, env, [(block's C, st index, picked StForm)]): one model build,
+  the evaluation without and with taps."""
   from ldm_tf2_amd.unet import UNet
   c = BR.unet_case(model)
   env = c["env"]
@@ -125,7 +146,8 @@ def _evaluate(dev, monkeypatch, model, dtype, kw, form):
   with pytest.raises(ValueError):
     u.forward(x, out=out, taps={}, **fkw)
   monkeypatch.undo()
-  return calls, n_up2, taps, env
+  assert [i for i, _ in u.forms()] == list(range(len(u.sts))), "every transformer block records the form it took"
+  return calls, n_up2, taps, env, [(u.sts[i].c, i, f) for i, f in u.forms()]
 
 
 def _figures(case, taps, env, dtype, what):
@@ -158,7 +180,8 @@ def test_unet_stages(dev, monkeypatch, model, dtype, name, form):
   if model == "B":
     # the constructor's own thresholds: 1024 rows are below every one, the per-layer launches without the fold
     must, must_not, extra = ("ldm_attention", "ldm_layernorm"), ("ldm_attention_ms",) + PANEL, None
-  calls, n_up2, taps, env = _evaluate(dev, monkeypatch, model, dtype, {} if model == "B" else dict(SMALL, **kw), form)
+  calls, n_up2, taps, env, picked = _evaluate(dev, monkeypatch, model, dtype,
+                                              {} if model == "B" else dict(SMALL, **kw), form)
   hist = {c: calls.count(c) for c in sorted(set(calls))}
   print(f"CALLS {model}-{BR.TAG[dtype]}-{name}-{form}: {hist} conv3x3_up2={n_up2}")
   # ---- the form is the one it is named for
@@ -167,6 +190,14 @@ def test_unet_stages(dev, monkeypatch, model, dtype, name, form):
   for m in must_not:
     assert m not in calls, f"{name}: {m} was called"
   assert (n_up2 > 0) == (name != "gather-upsample")
+  print(f"FORMS {model}-{BR.TAG[dtype]}-{name}-{form}: " + " ".join(f"{i}:C{c}:{'/'.join(map(str, f))}" for c, i, f in picked))
+  for c, i, f in picked:
+    if model == "A":
+      assert tuple(f[:4]) == (PICKED_BF16 if dtype == BF16 else PICKED_F32)[name][c], (name, c, i, f)
+    else:
+      assert (f.norm, f.ms, f.rest) == ("separate", False, "ffproj" if dtype == BF16 else "layers"), (c, i, f)
+    # a pair leaves its common prefix in its first block, by copies unless that block is ONE launch over half the rows
+    assert f.leave_prefix == (form == "paired" and i == 0 and f.rest != "block"), (name, form, c, i, f)
   key = (model, dtype, form)
   if name == "default":
     _BASE[key] = calls
