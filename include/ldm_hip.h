@@ -774,6 +774,41 @@ int ldm_contrast_mask(const float* acc, float* mask_out, float* mean_out, float*
 int ldm_store_row(const float* src, float* table, int64_t row_stride, int rows, const int32_t* index, int index_sign,
                   int index_bias, int64_t n, void* stream);
 
+/*
+ * Push-pull hole filling: out [B][H][W][c] float32 = x [B][H][W][c] float32 with every cell the
+ * keep mask m = keep [B][H][W] float32 (1 = keep) does not keep replaced by a smooth continuation of the kept ones: the
+ * start of an outpainted border or of a regenerated region ("masked content: fill").
+ *   Level 0: a_0 = x, w_0 = clamp(m, 0, 1), a NaN in m counting as 0.
+ *   Pull, level l -> l+1 until the level is 1 x 1 (L = ceil(log2(max(H, W))) levels; none for a 1 x 1 image):
+ *     H_{l+1} = ceil(H_l / 2), W_{l+1} = ceil(W_l / 2); coarse cell (i, j) reads its in-bounds children (2i + dy,
+ *     2j + dx) in the order (0,0), (0,1), (1,0), (1,1): s += w, v = fma(w, a, v) per channel, a child of weight 0
+ *     contributing nothing whatever its value (a select, not 0 * a: a NaN in a hole does not leak);
+ *     a_{l+1} = s > 0 ? v / s : 0 (one correctly rounded division), w_{l+1} = min(s, 1).
+ *   Push, from f_L = a_L (for a 1 x 1 image: x where w_0 > 0, else 0) down to f_0.  At fine cell (y, x): cy = y >> 1,
+ *     ny = clamp(cy + (y & 1 ? +1 : -1), 0, H_{l+1} - 1), columns alike; top = fma(0.25, f[cy][nx], 0.75 f[cy][cx]),
+ *     bot = fma(0.25, f[ny][nx], 0.75 f[ny][cx]), u = fma(0.25, bot, 0.75 top);
+ *     f_l = a_l (the bits) where w_l == 1, u where w_l == 0, fma(w_l, a_l - u, u) otherwise.
+ *   out = f_0.  Kept cells (m >= 1) come out bit for bit, an all-zero mask gives zeros, one kept cell a constant image.
+ * All float32; a thread owns an output element of its level: no atomics, the result is deterministic.
+ *
+ * workspace: ldm_pushpull_workspace_bytes(B, H, W, c) bytes of the caller's (levels 1 .. L of a and w; 0 bytes and a
+ * NULL pointer for a 1 x 1 image).  Every element read is written first, whatever the workspace held.  out == x is
+ * allowed (level 0's push reads x at its own cell only); any other overlap is not.  Nothing is allocated or
+ * synchronised.
+ *
+ * Launches: lds_tail = 0 gives every level its own pull and its own push launch (2 L in all).  lds_tail = 1 (the
+ * product's setting) replaces, from the first level with H_l <= 32 and W_l <= 32 on, all remaining pulls and all
+ * pushes back up to that level by ONE launch of one workgroup per sample that keeps those levels in LDS (under 28 KB
+ * at c = 4; c > 10 would not fit 64 KB and runs as lds_tail = 0): 7 launches instead of 16 for a 256 x 256 image.  Both
+ * settings run the same operations in the same order and give the same bits, as do the two paths of the launched
+ * levels (channel quads when c % 4 == 0 and x, out and workspace are 16-byte aligned, else element-wise).
+ * LDM_ERR_ARG, nothing launched: a null x, keep or out; a null workspace unless H == W == 1; B, H, W or c below 1;
+ * H W c above 2^31 - 1; lds_tail other than 0 or 1.
+ */
+size_t ldm_pushpull_workspace_bytes(int B, int H, int W, int c);
+int ldm_pushpull_fill(const float* x, const float* keep, float* out, float* workspace, int B, int H, int W, int c,
+                      int lds_tail, void* stream);
+
 /* decode_first_stage prologue (model_runners.py:426 + autoencoder.py:362,434):
  * out = Dense_{C->C}(latents / scale_factor), C <= 8; float32 in, out_dtype out. */
 int ldm_post_quant(const float* latents, float scale_factor, const float* kernel_io,

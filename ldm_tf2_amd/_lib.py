@@ -138,6 +138,8 @@ SIGNATURES = {
     "ldm_contrast_mask_supported": (c_i32, [c_i32, c_i32, c_i32]),
     "ldm_contrast_mask": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_i32, c_vp]),
     "ldm_store_row": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_i64, c_vp]),
+    "ldm_pushpull_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
+    "ldm_pushpull_fill": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "ldm_post_quant": (c_i32, [c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp]),
     "ldm_groupnorm_fused_supported": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32]),
     "ldm_groupnorm_fused_form": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i32)]),

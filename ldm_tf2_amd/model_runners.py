@@ -72,6 +72,12 @@ conditional contexts, ldm_eps_contrast_accum) and thresholds the map on the devi
 ddim_invert_loop(trajectory=True) stores every inversion level with one ldm_store_row launch inside its captured step;
 the sampling loop's masked blend then reads that trajectory where the img2img loop reads q_sample(z0, Q).  Three graph
 slots of their own; without the keywords every key, launch and graph is the one it was.
+
+ddim_p_sample_loop_outpaint and masked_content="fill" on ddim_p_sample_loop_img2img choose what
+a regenerated region starts from: the image the encoder sees gets that region -- the new border of an outpainted
+canvas, or the mask's hole -- filled with a smooth continuation of the kept pixels by a push-pull image pyramid
+(ldm_pushpull_fill), one eager call in front of the encoder.  The loop behind it is the masked img2img loop as it is:
+no new graph, slot or state.
 """
 from __future__ import annotations
 
@@ -232,6 +238,59 @@ def latent_mask_fit(pixel_mask, size):
   for x in range(w):
     out[:, :, x] = rows[:, :, (x * Ws) // w:-((-(x + 1) * Ws) // w)].all(axis=2)
   return out.astype(np.float32)
+
+
+MASKED_CONTENTS = ("original", "fill")   # what a regenerated region starts from
+
+
+def fill_keep_mask(mask, src, size, f, fit="stretch"):
+  """The keep weights float32 [B,H,W] (B = 1 for a 2-D mask) that masked_content="fill" hands ops.pushpull_fill with
+  the images [B,H,W,3] the encoder sees, `size` = (H, W).  `mask` is the img2img loop's:
+    a latent mask [B,H/f,W/f] (or [H/f,W/f]): every cell's value repeated over its f x f pixels;
+    a pixel mask at the source images' extents `src` ([B,Hs,Ws] or [Hs,Ws], nonzero = keep): brought to the canvas the
+      way the images are -- with `fit` "crop" the same centred box (resample.crop_box) -- and canvas pixel y covers
+      the source rows floor(y Hs / H) .. ceil((y + 1) Hs / H) - 1, columns alike (latent_mask_fit's rule at pixel
+      resolution): the weight is 1 exactly where every source pixel the canvas pixel covers is kept, else 0.
+  Any other shape is a ValueError."""
+  H, W = (int(v) for v in size)
+  src = tuple(int(v) for v in src)
+  if H % f or W % f:
+    raise ValueError(f"the filled canvas {(H, W)} must have extents that are multiples of {f}")
+  h, w = H // f, W // f
+  m = np.asarray(mask.cpu() if isinstance(mask, torch.Tensor) else mask)
+  shape = m.shape
+  if m.ndim == 2:
+    m = m[None]
+  if m.ndim == 3 and m.shape[1:] == (h, w):
+    return np.repeat(np.repeat(m.astype(np.float32), f, axis=1), f, axis=2)
+  if m.ndim != 3 or m.shape[1:] != src:
+    raise ValueError(f"mask of shape {shape} is neither a latent mask [B,{h},{w}] (or [{h},{w}]) nor a pixel mask "
+                     f"at the init images' size [B,{src[0]},{src[1]}] (or [{src[0]},{src[1]}])")
+  if fit == "crop" and src != (H, W):
+    y0, x0, hc, wc = crop_box(src, (H, W))
+    m = m[:, y0:y0 + hc, x0:x0 + wc]
+  return latent_mask_fit(m, (H, W))
+
+
+def outpaint_geometry(image_hw, pad, f, div=1):
+  """Outpainting's canvas: an image of `image_hw` = (H, W) pixels grows by `pad` = (top,
+  bottom, left, right) pixels, each at least 0 and not all 0.  Returns ((Hc, Wc), (y0, x0, H, W)): the canvas size and
+  the box the image takes on it.  Both canvas extents must be positive multiples of f * div (`f` the autoencoder's
+  pixels per latent cell, `div` = 2^levels for a U-Net that halves its input `levels` times): ValueError otherwise."""
+  if np.ndim(image_hw) != 1 or len(image_hw) != 2 or any(int(v) != v or v < 1 for v in image_hw):
+    raise ValueError(f"image_hw must be (H, W) in pixels, got {image_hw!r}")
+  if np.ndim(pad) != 1 or len(pad) != 4 or any(isinstance(v, bool) or int(v) != v for v in pad):
+    raise ValueError(f"pad must be (top, bottom, left, right) in pixels, got {pad!r}")
+  H, W = (int(v) for v in image_hw)
+  top, bottom, left, right = (int(v) for v in pad)
+  if min(top, bottom, left, right) < 0 or max(top, bottom, left, right) == 0:
+    raise ValueError(f"pad {(top, bottom, left, right)}: every side must be at least 0 and one of them positive")
+  Hc, Wc = H + top + bottom, W + left + right
+  f, div = int(f), int(div)
+  if Hc % (f * div) or Wc % (f * div):
+    raise ValueError(f"outpaint canvas {(Hc, Wc)}: the autoencoder maps {f} pixels to a latent cell and the U-Net halves "
+                     f"its input {div.bit_length() - 1} times, the extents must be positive multiples of {f * div}")
+  return (Hc, Wc), (top, left, H, W)
 
 
 def window_origins(L, l, s):
@@ -1433,7 +1492,7 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
                                  mask=None, encode_noise=None, q_noises=None, noises=None, seed=0,
                                  first_sample_index=0, record=None, guidance_interval=None, image_size=None,
                                  fit="stretch", resample="lanczos3", preview_freq=None, on_preview=None,
-                                 attn_maps=None, attn_layers=None):
+                                 attn_maps=None, attn_layers=None, masked_content="original"):
     """img2img (SDEdit) and masked inpainting on the DDIM loop.
     cond_model_inputs: token ids [uncond x B; cond x B].  init_images [B,H,W,3] (or [H,W,3], tiled) float32
     in [-1, 1].  z0 = get_latents(init_images, encode_noise); k = int(strength * N); the loop starts from
@@ -1450,19 +1509,33 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     whose extents are the latent ones is read as a latent mask.  `preview_freq` / `on_preview` as in
     ddim_p_sample_loop (the strips have a slot for every multiple of q below N; the loop writes those it reaches, up
     to (k-1) // q, and leaves the others 0); `attn_maps` / `attn_layers` too (the weights stay indexed by DDIM index;
-    weight_sum covers the k indices run).  Returns the decoded images; the final latents stay in self._xt."""
+    weight_sum covers the k indices run).  `masked_content`: "original" (default: everything
+    above, unchanged) starts the regenerated region from the init image's own latents; "fill" (needs `mask`) first
+    replaces that region of the image the encoder sees -- after `image_size` fitting -- by a smooth continuation of
+    the kept pixels (ops.pushpull_fill, keep weights by fill_keep_mask), one eager call before the encoder.
+    Returns the decoded images; the final latents stay in self._xt."""
     size = self._image_size(image_size, fit, resample)
+    if masked_content not in MASKED_CONTENTS:
+      raise ValueError(f"masked_content must be one of {MASKED_CONTENTS}, got {masked_content!r}")
+    if masked_content == "fill" and mask is None:
+      raise ValueError("masked_content 'fill' fills the region a mask regenerates: it needs mask")
     gsched = self._guidance(guidance_scale, guidance_interval)
     n = len(self._ddim_steps)
     k = img2img_start(strength, n)
     B = len(cond_model_inputs) // 2
     imgs = self._init_images(init_images, B)
+    keep = None
+    if masked_content == "fill":
+      src = tuple(int(v) for v in imgs.shape[1:3])
+      keep = fill_keep_mask(mask, src, src if size is None else size, self._pixel_factor(), fit)
     if mask is not None and size is not None:
       mask = self._fit_mask(mask, tuple(imgs.shape[1:3]), size, fit)
     if mask is not None:
       mask = self._latent_mask(mask, B)
     if size is not None:
       imgs = self._fit_images(imgs, size, fit, resample)
+    if keep is not None:
+      imgs = self._fill_images(imgs, keep)
     context = self._cond_stage_model(cond_model_inputs)
     z0 = self.get_latents(imgs, noise=encode_noise, seed=seed, first_sample_index=first_sample_index)
     return self._sdedit(context, z0, k, guidance_scale, gsched, mask, q_noises, noises, seed, first_sample_index,
@@ -1508,6 +1581,48 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
 
     return self._denoise(k, set_start, guidance_scale, gsched, noise_table, masked, rng, record,
                          preview_freq=preview_freq, on_preview=on_preview, attn_maps=attn_maps, attn_layers=attn_layers)
+
+  # ---- outpainting and masked-content fill ------------------------------
+  def _fill_images(self, imgs, keep):
+    """imgs [B,H,W,3] with the cells `keep` [B,H,W] (or [1,H,W], tiled; 1 = keep) does not keep filled from the kept
+    ones on the device (ops.pushpull_fill): one eager call in front of the encoder, no state of the sampler's."""
+    x = imgs.to(self.device, torch.float32).contiguous()
+    m = _as_tensor(keep).to(self.device)
+    m = m.expand(x.shape[0], *m.shape[1:]).contiguous()
+    return ops.pushpull_fill(x, m)
+
+  def ddim_p_sample_loop_outpaint(self, cond_model_inputs, images, pad, guidance_scale=5., strength=1.0,
+                                  masked_content="fill", encode_noise=None, q_noises=None, noises=None, seed=0,
+                                  first_sample_index=0, record=None, guidance_interval=None, preview_freq=None,
+                                  on_preview=None, attn_maps=None, attn_layers=None):
+    """Outpainting: `images` [B,H,W,3] (or [H,W,3], tiled) float32 in [-1, 1] grow by `pad` =
+    (top, bottom, left, right) pixels (outpaint_geometry: both canvas extents multiples of f * 2^levels).  The images
+    are placed on the canvas, the border -- zeros, i.e. grey, with `masked_content` "original" -- is filled with a
+    smooth continuation of the images' pixels ("fill", the default; ops.pushpull_fill), the canvas is encoded and the
+    masked img2img loop runs on it with the latent mask that keeps the cells lying wholly inside the images
+    (latent_mask): the loop of ddim_p_sample_loop_img2img(canvas, mask=...), its graphs, state and launches, with one
+    eager fill in front of the encoder.  The other keywords as in ddim_p_sample_loop_img2img.  Returns the decoded
+    canvas [B,H+top+bottom,W+left+right,3]; the final latents stay in self._xt."""
+    if masked_content not in MASKED_CONTENTS:
+      raise ValueError(f"masked_content must be one of {MASKED_CONTENTS}, got {masked_content!r}")
+    gsched = self._guidance(guidance_scale, guidance_interval)
+    k = img2img_start(strength, len(self._ddim_steps))
+    B = len(cond_model_inputs) // 2
+    imgs = self._init_images(images, B)
+    f, div = self._pixel_factor(), 1 << max(getattr(self._unet, "skip_lvl", (0,)))
+    (Hc, Wc), (y0, x0, H, W) = outpaint_geometry(tuple(imgs.shape[1:3]), pad, f, div)
+    canvas = torch.zeros(B, Hc, Wc, 3, dtype=torch.float32, device=self.device)
+    canvas[:, y0:y0 + H, x0:x0 + W] = imgs.to(self.device)
+    keep = np.zeros((1, Hc, Wc), dtype=np.float32)
+    keep[:, y0:y0 + H, x0:x0 + W] = 1.
+    if masked_content == "fill":
+      canvas = self._fill_images(canvas, keep)
+    mask = self._latent_mask(latent_mask(keep, f)[0], B)
+    context = self._cond_stage_model(cond_model_inputs)
+    z0 = self.get_latents(canvas, noise=encode_noise, seed=seed, first_sample_index=first_sample_index)
+    return self._sdedit(context, z0, k, guidance_scale, gsched, mask, q_noises, noises, seed, first_sample_index,
+                        record, preview_freq=preview_freq, on_preview=on_preview, attn_maps=attn_maps,
+                        attn_layers=attn_layers)
 
   # ---- two-pass high-resolution sampling (DESIGN.md section 14) --------------------------------
   def ddim_p_sample_loop_hires(self, cond_model_inputs, shape, hires_shape, strength=0.5, resize="bilinear",

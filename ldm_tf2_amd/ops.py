@@ -22,7 +22,7 @@ __all__ = [
     "time_embedding", "gemv", "cfg_ddim_update", "cfg_ddim_update_masked", "cfg_plms_update", "q_sample",
     "philox_u32", "normal_fill", "q_sample_rng", "cfg_ddim_update_rng", "cfg_plms_update_rng", "cfg_ms_update",
     "cfg_ms_update_rng", "cfg_sched_update", "cfg_ddim_invert_update", "window_gather", "window_fold", "window_gather_ex", "window_fold_ex", "wrap_pad", "resize_nhwc", "resample_nhwc", "latent_preview", "xattn_map", "xattn_map_supported",
-    "eps_contrast_accum", "contrast_mask", "contrast_mask_supported", "store_row", "post_quant", "vq_nearest", "embedding",
+    "eps_contrast_accum", "contrast_mask", "contrast_mask_supported", "store_row", "pushpull_fill", "pushpull_workspace", "post_quant", "vq_nearest", "embedding",
     "minmax_u8", "cast",
 ]
 
@@ -1141,6 +1141,39 @@ def resample_nhwc(x, size, filter="lanczos3", out=None):
   check(lib.ldm_resample_nhwc(_ptr(_f32(x, "x")), _ptr(tmp), _ptr(_f32(out, "out")), B, H, W, c, Ho, Wo, _ptr(xs),
                               _ptr(xw), xt, _ptr(ys), _ptr(yw), yt, _stream()), "ldm_resample_nhwc")
   return out
+
+
+_pushpull_ws = {}
+
+
+def pushpull_fill(x, keep, out=None, lds_tail=True):
+  """Push-pull hole filling (include/ldm_hip.h): x [B,H,W,c] float32, keep [B,H,W] float32 (1 =
+  keep) -> [B,H,W,c] float32, the kept cells bit for bit and every other cell a smooth continuation of them.
+  `out`: where the result goes (contiguous; allocated when omitted; `x` itself is allowed).  `lds_tail` False gives
+  every pyramid level its own launches (same bits).  The workspace is kept per (B, H, W, c, device)."""
+  assert x.dim() == 4 and x.is_contiguous(), (tuple(x.shape), x.stride())
+  B, H, W, c = (int(v) for v in x.shape)
+  assert keep.is_contiguous() and tuple(keep.shape) == (B, H, W), (tuple(keep.shape), (B, H, W))
+  if out is None:
+    out = torch.empty(B, H, W, c, dtype=torch.float32, device=x.device)
+  else:
+    assert out.is_contiguous() and tuple(out.shape) == (B, H, W, c), (tuple(out.shape), (B, H, W, c))
+  _ptr(x)                                        # (a host tensor is refused before the workspace is made)
+  ws = pushpull_workspace(B, H, W, c, x.device)
+  check(lib.ldm_pushpull_fill(_ptr(_f32(x, "x")), _ptr(_f32(keep, "keep")), _ptr(_f32(out, "out")), _ptr(ws), B, H, W,
+                              c, int(bool(lds_tail)), _stream()), "ldm_pushpull_fill")
+  return out
+
+
+def pushpull_workspace(B, H, W, c, device):
+  """pushpull_fill's workspace for this shape on `device`: a float32 tensor of ldm_pushpull_workspace_bytes, made on
+  first use and kept (None for a 1 x 1 image, which needs none).  The launcher writes every element before it reads
+  it, so what the tensor holds between calls does not matter."""
+  key = (B, H, W, c, torch.device(device))
+  if key not in _pushpull_ws:
+    n = int(lib.ldm_pushpull_workspace_bytes(B, H, W, c))
+    _pushpull_ws[key] = torch.empty(n // 4, dtype=torch.float32, device=device) if n else None
+  return _pushpull_ws[key]
 
 
 def latent_preview(lat_a, proj, frames_a, freq, index=None, index_bias=0, lat_b=None, frames_b=None, scale=1,

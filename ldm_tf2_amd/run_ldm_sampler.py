@@ -98,6 +98,16 @@ per-token maps, float32 [B,Tk,H,W], as `attention_maps.npy` and the prompt's wor
 `attention_maps`.  The txt2img and img2img loops take it; `guidance_interval`, a list `guidance_scale`,
 `preview_freq`, `window`, `hires_shape`, `source_prompt` and `sample_save_progress` cannot be combined with it.
 Without `attention_maps` nothing changes.
+
+Outpainting and masked content: optional `ldm_sampling` key `outpaint: [top, bottom, left,
+right]` (pixels, each at least 0 and not all 0; needs `init_image`).  The init image is placed on a canvas that many
+pixels larger -- `latent_shape` is the canvas's, so the grown image must have f times its extents -- the new border is
+filled with a smooth continuation of the image (a push-pull image pyramid on the device), and the masked img2img loop
+regenerates the border while it keeps the image; `strength` defaults to 1.0 here.  `mask`, `window`, `hires_shape`,
+`source_prompt`, `sample_save_progress` and an `init_fit` other than `exact` cannot be combined with it.  Optional key
+`masked_content`, `original` (default: a regenerated region starts from the init image's own content, as above) or
+`fill` (it starts from the same smooth continuation of the kept pixels; needs `mask` or `outpaint`, where it is the
+default); needs `init_image`, and `source_prompt` cannot be combined with it.  Without these keys nothing changes.
 """
 from __future__ import annotations
 
@@ -112,8 +122,8 @@ import yaml
 from . import ops
 from .autoencoder import AutoencoderKL, AutoencoderVQ
 from ._lib import RESAMPLE_FILTERS
-from .model_runners import (FITS, PREVIEW_MODES, RESIZE_MODES, WINDOW_WEIGHTS, LatentDiffusionModelSampler,
-                            latent_mask, window_and_stride)
+from .model_runners import (FITS, MASKED_CONTENTS, PREVIEW_MODES, RESIZE_MODES, WINDOW_WEIGHTS,
+                            LatentDiffusionModelSampler, latent_mask, window_and_stride)
 from .tokenizer import get_token_ids
 from .transformer import TransformerModel
 from .unet import UNet
@@ -472,6 +482,64 @@ def attention_map_kwargs(config):
   return {} if am is None else dict(attn_maps=am["weights"])
 
 
+def outpaint_pad(config):
+  """`ldm_sampling.outpaint: [top, bottom, left, right]` (pixels; the reference's YAML has no
+  such key), checked: None without the key, else the outpaint loop's `pad`.  The loop grows `init_image`; it has no
+  mask of the caller's, windows, second pass, source prompt or progress frames, and takes the image as it is."""
+  samp = config["ldm_sampling"]
+  pad = samp.get("outpaint")
+  if pad is None:
+    return None
+  if not isinstance(pad, (list, tuple)) or len(pad) != 4 or \
+      any(isinstance(v, bool) or not isinstance(v, int) or v < 0 for v in pad) or not any(pad):
+    raise ValueError("ldm_sampling.outpaint must be [top, bottom, left, right], ints of at least 0 and not all 0, "
+                     f"got {pad!r}")
+  if not samp.get("init_image"):
+    raise ValueError("ldm_sampling.outpaint needs ldm_sampling.init_image")
+  for key in ("mask", "window", "hires_shape", "source_prompt", "sample_save_progress"):
+    if samp.get(key) is not None and samp.get(key) is not False:
+      raise ValueError(f"ldm_sampling.outpaint cannot be combined with ldm_sampling.{key}")
+  if samp.get("init_fit", "exact") != "exact":
+    raise ValueError("ldm_sampling.outpaint cannot be combined with ldm_sampling.init_fit")
+  return tuple(pad)
+
+
+def masked_content_name(config):
+  """`ldm_sampling.masked_content: original | fill` (the reference's YAML has no such key),
+  checked: None without the key.  It belongs to the img2img loop with a mask and to the outpaint loop."""
+  samp = config["ldm_sampling"]
+  mc = samp.get("masked_content")
+  if mc is None:
+    return None
+  if mc not in MASKED_CONTENTS:
+    raise ValueError(f"ldm_sampling.masked_content must be one of {MASKED_CONTENTS}, got {mc!r}")
+  if not samp.get("init_image"):
+    raise ValueError("ldm_sampling.masked_content needs ldm_sampling.init_image")
+  if samp.get("source_prompt") is not None:
+    raise ValueError("ldm_sampling.masked_content cannot be combined with ldm_sampling.source_prompt")
+  if mc == "fill" and samp.get("mask") is None and samp.get("outpaint") is None:
+    raise ValueError("ldm_sampling.masked_content 'fill' needs ldm_sampling.mask or ldm_sampling.outpaint")
+  return mc
+
+
+def outpaint_call(config, token_ids, seed, extra):
+  """The outpaint loop's call: `init_image` grown by `outpaint` must have f times the extents of `latent_shape`."""
+  samp = config["ldm_sampling"]
+  pad = outpaint_pad(config)
+  images = _init_images(samp)
+  f = downsampling_factor(config)
+  want = (f * samp["latent_shape"][1], f * samp["latent_shape"][2])
+  got = (images.shape[-3] + pad[0] + pad[1], images.shape[-2] + pad[2] + pad[3])
+  if got != want:
+    raise ValueError(f"ldm_sampling.outpaint: init_image {images.shape[-3:-1]} grown by {list(pad)} is {got}, "
+                     f"latent_shape needs {want}")
+  kwargs = dict(strength=float(samp.get("strength", 1.0)), seed=seed, **guidance_kwargs(config), **extra)
+  mc = masked_content_name(config)
+  if mc is not None:
+    kwargs["masked_content"] = mc
+  return "ddim_p_sample_loop_outpaint", (token_ids, images, pad, samp["guidance_scale"]), kwargs
+
+
 def sampling_call(config, token_ids, seed, source_ids=None):
   """(sampler method name, positional args, kwargs) of the call main() makes for `config`.  `source_ids`: the token
   ids of `ldm_sampling.source_prompt` when the key is there."""
@@ -481,6 +549,8 @@ def sampling_call(config, token_ids, seed, source_ids=None):
   preview = preview_kwargs(config)               # (ValueError: a loop without previews, or a key without preview_freq)
   preview.update(attention_map_kwargs(config))   # (the heat maps go where the previews go, and refuse the same loops)
   edit_mask_kwargs(config)                       # (ValueError: a key without edit_mask, edit_mask without its prompt)
+  outpaint = outpaint_pad(config)                # (ValueError: a loop that cannot outpaint, whatever the order below)
+  masked_content = masked_content_name(config)
   for key in PANORAMA_WRAP_KEYS:
     if samp.get(key) is not None and samp.get("window") is None:
       raise ValueError(f"ldm_sampling.{key} needs ldm_sampling.window")
@@ -494,6 +564,8 @@ def sampling_call(config, token_ids, seed, source_ids=None):
     return "ddim_p_sample_loop_panorama", base, panorama_kwargs(config, seed)
   if samp.get("mask") is not None and not samp.get("init_image"):
     raise ValueError("ldm_sampling.mask needs ldm_sampling.init_image")
+  if outpaint is not None:
+    return outpaint_call(config, token_ids, seed, preview)
   if samp.get("init_image"):
     if samp.get("sample_save_progress"):
       raise ValueError("sample_save_progress is not supported with init_image")
@@ -507,6 +579,8 @@ def sampling_call(config, token_ids, seed, source_ids=None):
       else:
         lm = latent_mask(pm, downsampling_factor(config))
         kwargs["mask"] = lm[0] if pm.ndim == 2 else lm          # [h,w]: one mask, tiled over the batch
+    if masked_content is not None:
+      kwargs["masked_content"] = masked_content
     return "ddim_p_sample_loop_img2img", (token_ids, images, samp["guidance_scale"]), kwargs
   if samp.get("sample_save_progress"):
     return "ddim_p_sample_loop_progressive", base, dict(seed=seed, **guidance_kwargs(config))
