@@ -809,6 +809,53 @@ size_t ldm_pushpull_workspace_bytes(int B, int H, int W, int c);
 int ldm_pushpull_fill(const float* x, const float* keep, float* out, float* workspace, int B, int H, int W, int c,
                       int lds_tail, void* stream);
 
+/*
+ * Pixel-space paste-back after a masked decode, float32.  Pixel p is kept, P(p) = 1, iff
+ * keep(p) >= 1; anything else, a NaN included, is a hole.  keep is [B][H][W] with keep_bstride = H W, or one [H][W]
+ * mask for every sample with keep_bstride = 0; w_bstride alike.
+ *
+ * ldm_mask_feather: out [B][H][W] = w, the weight of the source pixels, a ramp that lies inside the kept region.
+ *   taps: g[0 .. 2r], r in [0, 48], the caller's (a Gaussian of sigma pixels, r = ceil(3 sigma), normalised to sum 1 in
+ *     float64 and rounded to float32; r = 0: the single tap 1).
+ *   e(p) = 1 iff every in-bounds pixel within Chebyshev distance r of p is kept (a row pass, then a column pass; pixels
+ *     outside the image count as kept, so the picture's border does not fade); q = 1 - e.
+ *   Hq(y, x) = sum_t g[t] q(y, x + t - r), V(y, x) = sum_t g[t] Hq(y + t - r, x): taps outside the image contribute
+ *     nothing; each sum is one fma chain in ascending t from 0.
+ *   w(p) = P(p) ? clamp(1 - V(p), 0, 1) : 0.  So w is exactly 0 on every hole, exactly 1 where no hole lies within
+ *     Chebyshev distance 2r, and r = 0 returns P.
+ *   lds_tile = 0 (the product's setting, the faster form where measured): four launches (erode rows, erode columns with the complement, blur rows, blur columns with the
+ *     select) through workspace, ldm_mask_feather_workspace_bytes(B, H, W) bytes of the caller's; every element read is
+ *     written first.  lds_tile = 1 with r <= 16: one launch, a workgroup per 32 x 32 output tile stages the (32 + 4r)^2
+ *     neighbourhood of P in LDS (bytes for P, the row erosion and q, floats for Hq: 27 648 bytes at r = 16) and runs the
+ *     same four passes there, the same taps in the same order; workspace is not touched and may be NULL.  lds_tile = 1
+ *     with r > 16 runs as lds_tile = 0.  Both give the same bits.
+ *   LDM_ERR_ARG, nothing launched: a null keep, taps or out; a null workspace on the four-launch path; B, H or W below
+ *     1; H W above 2^31 - 1; r outside [0, 48]; keep_bstride neither 0 nor at least H W; lds_tile other than 0 or 1.
+ *
+ * ldm_keep_stats: o, d [B][H][W][c] (the source and the decoded images), c <= 4.  stats [B][c][5] float64 = n, sum o,
+ *   sum o^2, sum d, sum d^2 over the pixels with P = 1; a pixel that is not kept is selected out, not multiplied by 0,
+ *   so a NaN in a hole does not leak.  partial: B x ldm_keep_stats_partials(H, W) x c x 5 floats of the caller's, the
+ *   float32 sums of one workgroup's chunk of pixels each (the chunk count depends on H W alone; thread stride, then
+ *   wave, then LDS; no atomics); a finalise launch adds them in ascending order in float64 and writes gain, offset
+ *   [B][c] float32: with var_x = (sum x^2 - (sum x)^2 / n) / n, a = sqrt(max(var_o, 0) / var_d) clamped to [0.5, 2],
+ *   a = 1 if n < 2 or var_d <= 1e-12, b = mean_o - a mean_d; a = 1, b = 0 if n = 0.
+ *   LDM_ERR_ARG: a null pointer; B (at most 65535), H, W or c below 1; c above 4; H W above 2^31 - 1; a bad stride.
+ *
+ * ldm_paste_back: d' = fma(a, d, b) per sample and channel with gain and offset (both or neither; NULL: d' = d, the
+ *   bits); out = w >= 1 ? o : (w <= 0 ? d' : fma(w, o - d', d')), selects: o in a hole is never read into the result.
+ *   out may be d.  Channel quads when c % 4 == 0 and o, d, out are 16-byte aligned, else element-wise; same bits.
+ *   LDM_ERR_ARG: a null o, d, w or out; gain without offset; B, H, W or c below 1; H W c above 2^31 - 1; a bad stride.
+ * Nothing is allocated or synchronised.
+ */
+size_t ldm_mask_feather_workspace_bytes(int B, int H, int W);
+int ldm_mask_feather(const float* keep, int64_t keep_bstride, const float* taps, int r, float* out, float* workspace,
+                     int B, int H, int W, int lds_tile, void* stream);
+int ldm_keep_stats_partials(int H, int W);
+int ldm_keep_stats(const float* o, const float* d, const float* keep, int64_t keep_bstride, float* partial,
+                   double* stats, float* gain, float* offset, int B, int H, int W, int c, void* stream);
+int ldm_paste_back(const float* o, const float* d, const float* w, int64_t w_bstride, const float* gain,
+                   const float* offset, float* out, int B, int H, int W, int c, void* stream);
+
 /* decode_first_stage prologue (model_runners.py:426 + autoencoder.py:362,434):
  * out = Dense_{C->C}(latents / scale_factor), C <= 8; float32 in, out_dtype out. */
 int ldm_post_quant(const float* latents, float scale_factor, const float* kernel_io,

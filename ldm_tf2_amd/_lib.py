@@ -140,6 +140,11 @@ SIGNATURES = {
     "ldm_store_row": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_i32, c_i32, c_i64, c_vp]),
     "ldm_pushpull_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
     "ldm_pushpull_fill": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "ldm_mask_feather_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
+    "ldm_mask_feather": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "ldm_keep_stats_partials": (c_i32, [c_i32, c_i32]),
+    "ldm_keep_stats": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "ldm_paste_back": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "ldm_post_quant": (c_i32, [c_vp, c_f32, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp]),
     "ldm_groupnorm_fused_supported": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32]),
     "ldm_groupnorm_fused_form": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i32)]),

@@ -78,6 +78,12 @@ a regenerated region starts from: the image the encoder sees gets that region --
 canvas, or the mask's hole -- filled with a smooth continuation of the kept pixels by a push-pull image pyramid
 (ldm_pushpull_fill), one eager call in front of the encoder.  The loop behind it is the masked img2img loop as it is:
 no new graph, slot or state.
+
+paste_back= / mask_feather= / color_match= on ddim_p_sample_loop_img2img and ddim_p_sample_loop_outpaint (DESIGN.md
+section 22) put the init images' own pixels back after the decode wherever the mask keeps them: a feathered weight map
+(ldm_mask_feather), optionally the gain and offset that match the decoded image to the originals on the kept pixels
+(ldm_keep_stats), and the blend (ldm_paste_back) -- three eager calls after decode_first_stage, nothing inside the
+captured step; without the keywords every call and bit is the one it was.
 """
 from __future__ import annotations
 
@@ -1492,7 +1498,8 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
                                  mask=None, encode_noise=None, q_noises=None, noises=None, seed=0,
                                  first_sample_index=0, record=None, guidance_interval=None, image_size=None,
                                  fit="stretch", resample="lanczos3", preview_freq=None, on_preview=None,
-                                 attn_maps=None, attn_layers=None, masked_content="original"):
+                                 attn_maps=None, attn_layers=None, masked_content="original", paste_back=False,
+                                 mask_feather=0., color_match=False):
     """img2img (SDEdit) and masked inpainting on the DDIM loop.
     cond_model_inputs: token ids [uncond x B; cond x B].  init_images [B,H,W,3] (or [H,W,3], tiled) float32
     in [-1, 1].  z0 = get_latents(init_images, encode_noise); k = int(strength * N); the loop starts from
@@ -1513,19 +1520,26 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     above, unchanged) starts the regenerated region from the init image's own latents; "fill" (needs `mask`) first
     replaces that region of the image the encoder sees -- after `image_size` fitting -- by a smooth continuation of
     the kept pixels (ops.pushpull_fill, keep weights by fill_keep_mask), one eager call before the encoder.
+    `paste_back` (needs `mask`; False: everything above, unchanged): after the decode the init
+    images' own pixels -- after `image_size` fitting, before any fill -- are put back bit for bit wherever
+    fill_keep_mask keeps them; `mask_feather` = sigma in pixels (0 .. 16) hides the seam with a ramp that lies inside
+    the kept region, `color_match` first applies to the decoded image the per-channel gain and offset that bring its
+    mean and variance over the kept pixels to the init images' (both need `paste_back`).  Three eager calls after the
+    decode, nothing inside the captured step; last_paste_weights() and last_color_match() return what they used.
     Returns the decoded images; the final latents stay in self._xt."""
     size = self._image_size(image_size, fit, resample)
     if masked_content not in MASKED_CONTENTS:
       raise ValueError(f"masked_content must be one of {MASKED_CONTENTS}, got {masked_content!r}")
     if masked_content == "fill" and mask is None:
       raise ValueError("masked_content 'fill' fills the region a mask regenerates: it needs mask")
+    paste = self._paste_args(paste_back, mask_feather, color_match, mask is not None)
     gsched = self._guidance(guidance_scale, guidance_interval)
     n = len(self._ddim_steps)
     k = img2img_start(strength, n)
     B = len(cond_model_inputs) // 2
     imgs = self._init_images(init_images, B)
     keep = None
-    if masked_content == "fill":
+    if masked_content == "fill" or paste is not None:
       src = tuple(int(v) for v in imgs.shape[1:3])
       keep = fill_keep_mask(mask, src, src if size is None else size, self._pixel_factor(), fit)
     if mask is not None and size is not None:
@@ -1534,13 +1548,15 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
       mask = self._latent_mask(mask, B)
     if size is not None:
       imgs = self._fit_images(imgs, size, fit, resample)
-    if keep is not None:
+    originals = imgs
+    if masked_content == "fill":
       imgs = self._fill_images(imgs, keep)
     context = self._cond_stage_model(cond_model_inputs)
     z0 = self.get_latents(imgs, noise=encode_noise, seed=seed, first_sample_index=first_sample_index)
-    return self._sdedit(context, z0, k, guidance_scale, gsched, mask, q_noises, noises, seed, first_sample_index,
-                        record, preview_freq=preview_freq, on_preview=on_preview, attn_maps=attn_maps,
-                        attn_layers=attn_layers)
+    images = self._sdedit(context, z0, k, guidance_scale, gsched, mask, q_noises, noises, seed, first_sample_index,
+                          record, preview_freq=preview_freq, on_preview=on_preview, attn_maps=attn_maps,
+                          attn_layers=attn_layers)
+    return images if paste is None else self._paste_back(images, originals, keep, *paste)
 
   def _sdedit(self, context, z0, k, guidance_scale, gsched, mask, q_noises, noises, seed, first_sample_index, record,
               preview_freq=None, on_preview=None, attn_maps=None, attn_layers=None):
@@ -1594,17 +1610,21 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
   def ddim_p_sample_loop_outpaint(self, cond_model_inputs, images, pad, guidance_scale=5., strength=1.0,
                                   masked_content="fill", encode_noise=None, q_noises=None, noises=None, seed=0,
                                   first_sample_index=0, record=None, guidance_interval=None, preview_freq=None,
-                                  on_preview=None, attn_maps=None, attn_layers=None):
+                                  on_preview=None, attn_maps=None, attn_layers=None, paste_back=False, mask_feather=0.,
+                                  color_match=False):
     """Outpainting: `images` [B,H,W,3] (or [H,W,3], tiled) float32 in [-1, 1] grow by `pad` =
     (top, bottom, left, right) pixels (outpaint_geometry: both canvas extents multiples of f * 2^levels).  The images
     are placed on the canvas, the border -- zeros, i.e. grey, with `masked_content` "original" -- is filled with a
     smooth continuation of the images' pixels ("fill", the default; ops.pushpull_fill), the canvas is encoded and the
     masked img2img loop runs on it with the latent mask that keeps the cells lying wholly inside the images
     (latent_mask): the loop of ddim_p_sample_loop_img2img(canvas, mask=...), its graphs, state and launches, with one
-    eager fill in front of the encoder.  The other keywords as in ddim_p_sample_loop_img2img.  Returns the decoded
-    canvas [B,H+top+bottom,W+left+right,3]; the final latents stay in self._xt."""
+    eager fill in front of the encoder.  `paste_back` / `mask_feather` / `color_match` put the
+    images' own pixels back after the decode: the originals are the canvas before the fill, the keep is the images'
+    box.  The other keywords as in ddim_p_sample_loop_img2img.  Returns the decoded canvas
+    [B,H+top+bottom,W+left+right,3]; the final latents stay in self._xt."""
     if masked_content not in MASKED_CONTENTS:
       raise ValueError(f"masked_content must be one of {MASKED_CONTENTS}, got {masked_content!r}")
+    paste = self._paste_args(paste_back, mask_feather, color_match, True)
     gsched = self._guidance(guidance_scale, guidance_interval)
     k = img2img_start(strength, len(self._ddim_steps))
     B = len(cond_model_inputs) // 2
@@ -1615,14 +1635,59 @@ class LatentDiffusionModelSampler(LatentDiffusionModel):
     canvas[:, y0:y0 + H, x0:x0 + W] = imgs.to(self.device)
     keep = np.zeros((1, Hc, Wc), dtype=np.float32)
     keep[:, y0:y0 + H, x0:x0 + W] = 1.
+    originals = canvas
     if masked_content == "fill":
       canvas = self._fill_images(canvas, keep)
     mask = self._latent_mask(latent_mask(keep, f)[0], B)
     context = self._cond_stage_model(cond_model_inputs)
     z0 = self.get_latents(canvas, noise=encode_noise, seed=seed, first_sample_index=first_sample_index)
-    return self._sdedit(context, z0, k, guidance_scale, gsched, mask, q_noises, noises, seed, first_sample_index,
-                        record, preview_freq=preview_freq, on_preview=on_preview, attn_maps=attn_maps,
-                        attn_layers=attn_layers)
+    images = self._sdedit(context, z0, k, guidance_scale, gsched, mask, q_noises, noises, seed, first_sample_index,
+                          record, preview_freq=preview_freq, on_preview=on_preview, attn_maps=attn_maps,
+                          attn_layers=attn_layers)
+    return images if paste is None else self._paste_back(images, originals, keep, *paste)
+
+  # ---- pixel-space paste-back ---------------------------------------------
+  @staticmethod
+  def _paste_args(paste_back, mask_feather, color_match, has_mask):
+    """The checked paste-back keywords as (sigma, color_match), None when `paste_back` is off.  Raises before anything
+    is allocated."""
+    from .feather import feather_radius
+    for name, v in (("paste_back", paste_back), ("color_match", color_match)):
+      if not isinstance(v, (bool, np.bool_)):
+        raise ValueError(f"{name} must be True or False, got {v!r}")
+    feather_radius(mask_feather)
+    if not paste_back:
+      if float(mask_feather) != 0.:
+        raise ValueError("mask_feather feathers the seam of the paste-back: it needs paste_back=True")
+      if color_match:
+        raise ValueError("color_match corrects the decoded image before the paste-back: it needs paste_back=True")
+      return None
+    if not has_mask:
+      raise ValueError("paste_back puts back the pixels a mask keeps: it needs mask")
+    return float(mask_feather), bool(color_match)
+
+  def _paste_back(self, images, originals, keep, sigma, color_match):
+    """The decoded `images` [B,H,W,3] with the pixels of `originals` that `keep` [B,H,W] (or [1,H,W]; kept iff >= 1)
+    keeps put back: ops.mask_feather, ops.keep_stats when `color_match`, ops.paste_back into `images`.  Eager, after
+    the decode; no state of the loop's."""
+    o = originals.to(self.device, torch.float32).contiguous()
+    m = _as_tensor(keep).to(self.device).contiguous()
+    w = ops.mask_feather(m, sigma)
+    gain = offset = None
+    if color_match:
+      _, gain, offset = ops.keep_stats(o, images, m)
+    self._paste_w, self._paste_cm = w, (gain, offset)
+    return ops.paste_back(o, images, w, gain, offset, out=images)
+
+  def last_paste_weights(self):
+    """The weight map w [B,H,W] (or [1,H,W], one map for every sample) float32 of the last paste-back: 1 where the
+    init images' pixels came back bit for bit, 0 where the decoded image stayed.  None before the first."""
+    return getattr(self, "_paste_w", None)
+
+  def last_color_match(self):
+    """(gain, offset), [B,3] float32 each, of the last paste-back with color_match=True; (None, None) without it, None
+    before the first paste-back."""
+    return getattr(self, "_paste_cm", None)
 
   # ---- two-pass high-resolution sampling (DESIGN.md section 14) --------------------------------
   def ddim_p_sample_loop_hires(self, cond_model_inputs, shape, hires_shape, strength=0.5, resize="bilinear",

@@ -22,7 +22,7 @@ __all__ = [
     "time_embedding", "gemv", "cfg_ddim_update", "cfg_ddim_update_masked", "cfg_plms_update", "q_sample",
     "philox_u32", "normal_fill", "q_sample_rng", "cfg_ddim_update_rng", "cfg_plms_update_rng", "cfg_ms_update",
     "cfg_ms_update_rng", "cfg_sched_update", "cfg_ddim_invert_update", "window_gather", "window_fold", "window_gather_ex", "window_fold_ex", "wrap_pad", "resize_nhwc", "resample_nhwc", "latent_preview", "xattn_map", "xattn_map_supported",
-    "eps_contrast_accum", "contrast_mask", "contrast_mask_supported", "store_row", "pushpull_fill", "pushpull_workspace", "post_quant", "vq_nearest", "embedding",
+    "eps_contrast_accum", "contrast_mask", "contrast_mask_supported", "store_row", "pushpull_fill", "pushpull_workspace", "mask_feather", "mask_feather_workspace", "keep_stats", "paste_back", "post_quant", "vq_nearest", "embedding",
     "minmax_u8", "cast",
 ]
 
@@ -1174,6 +1174,93 @@ def pushpull_workspace(B, H, W, c, device):
     n = int(lib.ldm_pushpull_workspace_bytes(B, H, W, c))
     _pushpull_ws[key] = torch.empty(n // 4, dtype=torch.float32, device=device) if n else None
   return _pushpull_ws[key]
+
+
+_feather_ws = {}
+_stats_ws = {}
+
+
+def _keep_arg(keep, B, H, W, what):
+  """A [B,H,W] or [1,H,W] float32 map as (tensor, batch stride): the one map is read for every sample."""
+  assert keep.dim() == 3 and keep.is_contiguous() and tuple(keep.shape[1:]) == (H, W) and keep.shape[0] in (1, B), \
+      (what, tuple(keep.shape), (B, H, W))
+  return _f32(keep, what), (H * W if keep.shape[0] == B and B > 1 else 0)
+
+
+def mask_feather(keep, sigma, out=None, lds_tile=False):
+  """The paste-back's weight map (include/ldm_hip.h): keep [B,H,W] float32 (kept iff >= 1) ->
+  w [B,H,W] float32, 0 on every hole, 1 deep inside the kept region, between them a ramp of `sigma` pixels (0 ..
+  16; taps by feather.device_taps) that lies inside the kept region; sigma = 0 returns the 0 / 1 map itself.
+  `out`: where the result goes (contiguous; allocated when omitted).  `lds_tile` False (the default: the faster form
+  where it was measured) runs the four launches through the workspace kept per (B, H, W,
+  device), True the one LDS-tiled launch (same bits)."""
+  from . import feather as F
+  assert keep.dim() == 3 and keep.is_contiguous(), (tuple(keep.shape), keep.stride())
+  B, H, W = (int(v) for v in keep.shape)
+  r = F.feather_radius(sigma)
+  if out is None:
+    out = torch.empty(B, H, W, dtype=torch.float32, device=keep.device)
+  else:
+    assert out.is_contiguous() and tuple(out.shape) == (B, H, W), (tuple(out.shape), (B, H, W))
+  _ptr(keep)                                     # (a host tensor is refused before the tables are made)
+  taps, r = F.device_taps(sigma, keep.device)
+  ws = mask_feather_workspace(B, H, W, keep.device)
+  check(lib.ldm_mask_feather(_ptr(_f32(keep, "keep")), H * W, _ptr(taps), r, _ptr(_f32(out, "out")), _ptr(ws), B, H, W,
+                             int(bool(lds_tile)), _stream()), "ldm_mask_feather")
+  return out
+
+
+def mask_feather_workspace(B, H, W, device):
+  """mask_feather's workspace for this shape on `device`: a float32 tensor of ldm_mask_feather_workspace_bytes, made
+  on first use and kept.  The launcher writes every element before it reads it."""
+  key = (B, H, W, torch.device(device))
+  if key not in _feather_ws:
+    n = int(lib.ldm_mask_feather_workspace_bytes(B, H, W))
+    _feather_ws[key] = torch.empty(max(n // 4, 1), dtype=torch.float32, device=device)
+  return _feather_ws[key]
+
+
+def keep_stats(o, d, keep):
+  """Statistics of the kept pixels (include/ldm_hip.h): o, d [B,H,W,c] float32 (c <= 4), keep
+  [B,H,W] or [1,H,W] float32 (kept iff >= 1) -> (stats [B,c,5] float64 = n, sum o, sum o^2, sum d, sum d^2 over the kept
+  pixels; gain [B,c], offset [B,c] float32 that bring d's mean and variance there to o's).  Fresh tensors every call;
+  the partial sums live in a buffer kept per (B, H, W, c, device)."""
+  assert o.dim() == 4 and o.is_contiguous(), (tuple(o.shape), o.stride())
+  B, H, W, c = (int(v) for v in o.shape)
+  assert d.is_contiguous() and tuple(d.shape) == (B, H, W, c), (tuple(d.shape), (B, H, W, c))
+  keep, kb = _keep_arg(keep, B, H, W, "keep")
+  _ptr(o)
+  key = (B, H, W, c, o.device)
+  if key not in _stats_ws:
+    n = B * max(int(lib.ldm_keep_stats_partials(H, W)), 1) * max(c, 1) * 5
+    _stats_ws[key] = torch.empty(n, dtype=torch.float32, device=o.device)
+  stats = torch.empty(B, c, 5, dtype=torch.float64, device=o.device)
+  gain = torch.empty(B, c, dtype=torch.float32, device=o.device)
+  offset = torch.empty(B, c, dtype=torch.float32, device=o.device)
+  check(lib.ldm_keep_stats(_ptr(_f32(o, "o")), _ptr(_f32(d, "d")), _ptr(keep), kb, _ptr(_stats_ws[key]), _ptr(stats),
+                           _ptr(gain), _ptr(offset), B, H, W, c, _stream()), "ldm_keep_stats")
+  return stats, gain, offset
+
+
+def paste_back(o, d, w, gain=None, offset=None, out=None):
+  """The paste-back (include/ldm_hip.h): o, d [B,H,W,c] float32 (the source and the decoded
+  images), w [B,H,W] or [1,H,W] float32 -> o where w >= 1 (the bits), d' where w <= 0, fma(w, o - d', d') between,
+  d' = gain d + offset per sample and channel ([B,c] float32 each, both or neither; None: d itself, the bits).
+  `out`: where the result goes (contiguous; allocated when omitted; `d` itself is allowed)."""
+  assert o.dim() == 4 and o.is_contiguous(), (tuple(o.shape), o.stride())
+  B, H, W, c = (int(v) for v in o.shape)
+  assert d.is_contiguous() and tuple(d.shape) == (B, H, W, c), (tuple(d.shape), (B, H, W, c))
+  w, wb = _keep_arg(w, B, H, W, "w")
+  for t, what in ((gain, "gain"), (offset, "offset")):
+    assert t is None or (t.is_contiguous() and tuple(t.shape) == (B, c)), (what, tuple(t.shape), (B, c))
+  if out is None:
+    out = torch.empty(B, H, W, c, dtype=torch.float32, device=o.device)
+  else:
+    assert out.is_contiguous() and tuple(out.shape) == (B, H, W, c), (tuple(out.shape), (B, H, W, c))
+  check(lib.ldm_paste_back(_ptr(_f32(o, "o")), _ptr(_f32(d, "d")), _ptr(w), wb, _ptr(_f32(gain, "gain")),
+                           _ptr(_f32(offset, "offset")), _ptr(_f32(out, "out")), B, H, W, c, _stream()),
+        "ldm_paste_back")
+  return out
 
 
 def latent_preview(lat_a, proj, frames_a, freq, index=None, index_bias=0, lat_b=None, frames_b=None, scale=1,

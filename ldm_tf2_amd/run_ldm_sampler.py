@@ -108,6 +108,13 @@ regenerates the border while it keeps the image; `strength` defaults to 1.0 here
 `masked_content`, `original` (default: a regenerated region starts from the init image's own content, as above) or
 `fill` (it starts from the same smooth continuation of the kept pixels; needs `mask` or `outpaint`, where it is the
 default); needs `init_image`, and `source_prompt` cannot be combined with it.  Without these keys nothing changes.
+
+Paste-back: optional `ldm_sampling` keys `paste_back: true` (after the decode the init image's
+own pixels are put back bit for bit wherever the mask keeps them), `mask_feather: sigma` (pixels, 0 .. 16: the seam is
+hidden by a ramp that lies inside the kept region) and `color_match: true` (the decoded image first gets the
+per-channel gain and offset that bring its mean and variance over the kept pixels to the init image's); the last two
+need `paste_back`.  Each needs `init_image` and `mask` or `outpaint`; `source_prompt`, `window` and `hires_shape`
+cannot be combined with them.  Three eager launches after the decode; without these keys nothing changes.
 """
 from __future__ import annotations
 
@@ -522,6 +529,45 @@ def masked_content_name(config):
   return mc
 
 
+PASTE_BACK_KEYS = ("paste_back", "mask_feather", "color_match")
+
+
+def paste_back_kwargs(config):
+  """`ldm_sampling.paste_back: true`, `mask_feather: sigma` (pixels, 0 .. 16) and `color_match: true` (DESIGN.md
+  section 22; the reference's YAML has no such keys), checked: the loops' keywords, nothing without the keys.  They
+  belong to the img2img loop with a mask and to the outpaint loop; `mask_feather` and `color_match` need `paste_back`."""
+  from .feather import feather_radius
+  samp = config["ldm_sampling"]
+  out = {}
+  for key in PASTE_BACK_KEYS:
+    v = samp.get(key)
+    if v is None:
+      continue
+    if key == "mask_feather":
+      if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise ValueError(f"ldm_sampling.mask_feather must be a number of pixels in [0, 16], got {v!r}")
+      try:
+        feather_radius(v)
+      except ValueError:
+        raise ValueError(f"ldm_sampling.mask_feather must be a number of pixels in [0, 16], got {v!r}") from None
+      v = float(v)
+    elif not isinstance(v, bool):
+      raise ValueError(f"ldm_sampling.{key} must be true or false, got {v!r}")
+    if not samp.get("init_image"):
+      raise ValueError(f"ldm_sampling.{key} needs ldm_sampling.init_image")
+    if samp.get("mask") is None and samp.get("outpaint") is None:
+      raise ValueError(f"ldm_sampling.{key} needs ldm_sampling.mask or ldm_sampling.outpaint")
+    for other in ("source_prompt", "window", "hires_shape"):
+      if samp.get(other) is not None:
+        raise ValueError(f"ldm_sampling.{key} cannot be combined with ldm_sampling.{other}")
+    out[key] = v
+  if not out.get("paste_back"):
+    for key in ("mask_feather", "color_match"):
+      if out.get(key):
+        raise ValueError(f"ldm_sampling.{key} needs ldm_sampling.paste_back")
+  return out
+
+
 def outpaint_call(config, token_ids, seed, extra):
   """The outpaint loop's call: `init_image` grown by `outpaint` must have f times the extents of `latent_shape`."""
   samp = config["ldm_sampling"]
@@ -537,6 +583,7 @@ def outpaint_call(config, token_ids, seed, extra):
   mc = masked_content_name(config)
   if mc is not None:
     kwargs["masked_content"] = mc
+  kwargs.update(paste_back_kwargs(config))
   return "ddim_p_sample_loop_outpaint", (token_ids, images, pad, samp["guidance_scale"]), kwargs
 
 
@@ -551,6 +598,7 @@ def sampling_call(config, token_ids, seed, source_ids=None):
   edit_mask_kwargs(config)                       # (ValueError: a key without edit_mask, edit_mask without its prompt)
   outpaint = outpaint_pad(config)                # (ValueError: a loop that cannot outpaint, whatever the order below)
   masked_content = masked_content_name(config)
+  paste = paste_back_kwargs(config)              # (ValueError: a loop without a paste-back, whatever the order below)
   for key in PANORAMA_WRAP_KEYS:
     if samp.get(key) is not None and samp.get("window") is None:
       raise ValueError(f"ldm_sampling.{key} needs ldm_sampling.window")
@@ -581,6 +629,7 @@ def sampling_call(config, token_ids, seed, source_ids=None):
         kwargs["mask"] = lm[0] if pm.ndim == 2 else lm          # [h,w]: one mask, tiled over the batch
     if masked_content is not None:
       kwargs["masked_content"] = masked_content
+    kwargs.update(paste)
     return "ddim_p_sample_loop_img2img", (token_ids, images, samp["guidance_scale"]), kwargs
   if samp.get("sample_save_progress"):
     return "ddim_p_sample_loop_progressive", base, dict(seed=seed, **guidance_kwargs(config))
